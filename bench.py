@@ -8,6 +8,15 @@ MI355X, data-parallel over N GPUs (one process per GPU, RCCL over xGMI).
     python bench.py --dtype bf16 --batch 64                 # configs[2]
     python bench.py --workload infer1080 [--dtype bf16]     # configs[4]: 1080p eval fwd, hipGraph
     python bench.py --dry-run --gpus 2                      # CPU/gloo launcher check only
+    python bench.py --full                                  # everything below, as one record
+    python bench.py --dump-outputs DIR                      # DIR/<name>.npy of the last timed step
+
+A plain run sets up, warms up, times K steps of ONE execution (the eager step;
+NSM_BENCH_STEP=graph: the hipGraph replay), writes its outputs if asked and
+prints the result line. --full adds the rest: the other execution beside the
+headline (the faster of the two is then the headline), the per-stage table and
+the roofline object from attribution steps, the secondary configs and the CPU
+baselines.
 
 Workload (BASELINE.json configs[1]): batch 8 per GPU, 7x512x512 fp32
 synthetic G-buffers (x ~ N(0,1), labels integers(0,256)/255), random-init
@@ -19,11 +28,12 @@ Step = forward + 0.9*L1 + backward + RCCL grad all-reduce (N > 1, overlapped
 with the backward) + the reference's whole step tail on the device
 (main.py:287-423: sanitise, per-parameter clips, clip_grad_norm_, AdamW).
 The step is timed eagerly, back to back, as an unchanged main.py loop runs it
-(weight gradients on the side stream), and at N = 1 also replayed from one HIP
-graph; both over K steps, the faster is the headline and the other is reported
-beside it ("graph" or "eager"; NSM_BENCH_STEP=eager|graph fixes the headline).
+(weight gradients on the side stream), and with --full at N = 1 also replayed
+from one HIP graph; both over K steps, the faster is the headline and the other
+is reported beside it ("graph" or "eager"; NSM_BENCH_STEP=eager|graph fixes the
+headline).
 
-Rank 0 prints ONE JSON line with the metric, a roofline object for the
+Rank 0 prints ONE JSON line with the metric and, with --full, a roofline object for the
 dominant convolution (conv6.conv.0 forward, 3x3 1024->1024: Winograd input
 transform + batched MFMA GEMM + output transform, timed as a whole with HIP
 events on its launch stream during the timed steps, priced on SURVEY.md
@@ -231,6 +241,29 @@ def load_stage_pmc(tag):
 
 def mean_ms(evs):
     return float(np.mean([a.elapsed_time(b) for a, b in evs])) if evs else float("nan")
+
+
+DUMP_MAX_ELEMS = 1 << 21   # per array: 8 MiB as float32, so a handful stay far below 64 MB
+
+
+def dump_array(t):
+    """A tensor as --dump-outputs stores it: float32 (float64 kept) on the
+    host, whole if it has at most DUMP_MAX_ELEMS elements, else that many of
+    its elements at fixed positions (seeded, sorted, the same in every run)."""
+    t = t.detach()
+    if t.numel() > DUMP_MAX_ELEMS:
+        idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), DUMP_MAX_ELEMS))
+        t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+    if t.dtype != torch.float64:
+        t = t.float()
+    return t.cpu().numpy()
+
+
+def write_dump(path, arrays):
+    """--dump-outputs: one <name>.npy per array."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def load_traffic(name):
@@ -493,10 +526,12 @@ def run_dry(args):
     for _ in range(args.warmup):
         step()
     elapsed = timed(step, args.steps, world, dev)
-    # the workloads a real run at this N measures (train: headline + secondary)
+    if args.dump_outputs and rank == 0:
+        write_dump(args.dump_outputs, {"buf": dump_array(buf)})
+    # the workloads a real run at this N measures (train: headline; --full: + secondary)
     plan = [{"config": "configs[1]", "role": "headline", "batch_per_gpu": args.batch,
              "global_batch": world * args.batch, "dtype": args.dtype}]
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         plan.append({"config": "configs[3]" if world > 1 else "configs[2] (= configs[3] at N=1)",
                      "role": "secondary", "batch_per_gpu": 64, "global_batch": world * 64,
                      "dtype": "bf16"})
@@ -520,12 +555,12 @@ def run_dry(args):
 def run_train(args):
     world, rank, dev = init_dist(args)
     res = train_measure(args, world, rank, dev)
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         sec = secondary_configs(args, world, rank, dev)
         if rank == 0:
             res["secondary"] = sec
     C, H, W = args.in_ch, args.res, args.res
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(C, H, W, frames=args.batch)
         if args.dtype in ("bf16", "f16"):
             res["cpu_baseline"]["sample"] += " (fp32: the reference's CPU path)"
@@ -600,7 +635,7 @@ def secondary_configs(args, world, rank, dev):
                 dict(workload="infer1080", dtype="f32", batch=1, steps=50, warmup=5),
                 dict(workload="infer256", dtype="f32", batch=1, steps=100, warmup=5)]
     for kw in kws:
-        a = _ap.Namespace(**{**base, "vgg": False, **kw})
+        a = _ap.Namespace(**{**base, "vgg": False, "dump_outputs": None, **kw})
         torch.cuda.empty_cache()
         if a.workload == "train":
             r = train_measure(a, world, rank, dev)
@@ -653,6 +688,11 @@ def train_measure(args, world, rank, dev):
     # as GraphedTrainStep does: loss.backward() would fill a fresh ones tensor
     # with an ATen kernel every step (and f16's loss * scale another)
     seed = torch.full((), loss_scale, dtype=torch.float32, device=dev)
+    # --dump-outputs: what the last eager step handed its caller (the output,
+    # the loss, the batch's gradient), kept by reference; off otherwise
+    full = getattr(args, "full", False)
+    keep = bool(getattr(args, "dump_outputs", None)) and rank == 0
+    last = {}
 
     def step():
         out = model(x)
@@ -665,10 +705,25 @@ def train_measure(args, world, rank, dev):
                 nsm_amd.allreduce_grads(model.parameters())
         opt.step()
         opt.zero_grad()
+        if keep:
+            last.update(out=out.detach(), loss=loss.detach(), x_grad=x.grad)
         # the reference's batch is a fresh tensor every step (setdata.py:325-326),
         # so its input gradient is written once, never accumulated into an old one
         x.grad = None
         return loss
+
+    def dump(graph_loss=None):
+        """The arrays of the last timed step (--dump-outputs): the state a
+        caller holds after it (parameters in module order as one vector, the
+        BN buffers likewise), its loss, and from the eager step the output
+        and the batch's gradient."""
+        if graph_loss is not None:
+            arrays = {"loss": graph_loss}
+        else:
+            arrays = dict(last)
+        arrays["params"] = torch.cat([p.detach().reshape(-1).float() for p in model.parameters()])
+        arrays["buffers"] = torch.cat([b.detach().reshape(-1).float() for b in model.buffers()])
+        write_dump(args.dump_outputs, {k: dump_array(v) for k, v in arrays.items()})
 
     for _ in range(args.warmup):
         step()
@@ -684,7 +739,11 @@ def train_measure(args, world, rank, dev):
     # is slow. eager / graph: that mode is the headline, the other timed over
     # min(K, 20) steps beside it. The kernel / stage timings below come from
     # eager steps of the same shapes.
+    # A plain run (no --full) times ONE execution over K steps: the eager
+    # step, or the replay under NSM_BENCH_STEP=graph.
     mode = os.environ.get("NSM_BENCH_STEP", "auto")
+    if not full and mode == "auto":
+        mode = "eager"
     head_graph = mode == "graph"
     graphed, dp_ms = None, None
     dp_tags = ("dp.bn_broadcast", "dp.allreduce_wait")
@@ -700,18 +759,23 @@ def train_measure(args, world, rank, dev):
             graphed()
         torch.cuda.synchronize()
         elapsed = timed(graphed, args.steps, world, dev)
+        if keep:
+            dump(graphed.loss)
         # the eager step beside it; only the DP waits carry events
         if dp:
             for t in dp_tags:
                 nops.PROBES[t] = []
-        side_elapsed = timed(step, side_steps, world, dev)
+        if full:
+            side_elapsed = timed(step, side_steps, world, dev)
     else:
         # eager timed steps: only the DP waits carry HIP events
         for t in dp_tags:
             nops.PROBES[t] = []
         elapsed = timed(step, args.steps, world, dev)
+        if keep:
+            dump()
         dp_ms = {t: mean_ms(nops.PROBES.pop(t, [])) for t in dp_tags}
-        if want_graph:
+        if want_graph and full:
             graphed = nsm_amd.GraphedTrainStep(model, crit, opt, x, y, loss_scale=loss_scale,
                                                warmup=1)
             for _ in range(args.warmup):
@@ -727,58 +791,70 @@ def train_measure(args, world, rank, dev):
     if dp_ms is None:
         dp_ms = {t: mean_ms(nops.PROBES.pop(t, [])) for t in dp_tags}
 
-    # attribution steps (not timed): kernel and stage times from HIP events
-    # with the weight gradients on the main stream, the configuration the
-    # per-stage counters are taken in (tools/stage_pmc.py, NSM_STAGE_MARKS),
-    # so each stage's bytes and time describe the same kernels
-    probe_tag = "conv6.conv.0.fwd"
-    nops.PROBES[probe_tag] = []
-    nops.PROBES[probe_tag + ".gemm"] = []
-    for st in STAGES:
-        nops.PROBES[st + ".fwd"] = []
-        nops.PROBES[st + ".bwd"] = []
-    nops.PROBES["vgg.fwd"] = []
-    nops.PROBES["vgg.30"] = []
-    nops.PROBES["vgg.30.gemm"] = []
-    from nsm_amd import unet as nunet
-    side_prev, nunet.WGRAD_STREAM = nunet.WGRAD_STREAM, False
-    try:
-        for _ in range(min(args.steps, 10)):
-            step()
-        torch.cuda.synchronize()
-    finally:
-        nunet.WGRAD_STREAM = side_prev
-    evs = nops.PROBES.pop(probe_tag)
-    kern_ms = mean_ms(evs)
-    gemm_ms = mean_ms(nops.PROBES.pop(probe_tag + ".gemm"))
-    vgg_evs = nops.PROBES.pop("vgg.fwd")
-    vgg30 = nops.PROBES.pop("vgg.30")
-    vgg30_gemm = mean_ms(nops.PROBES.pop("vgg.30.gemm"))
-    times = {}
-    for st in STAGES:
-        fw, bw = nops.PROBES.pop(st + ".fwd"), nops.PROBES.pop(st + ".bwd")
-        if fw and bw:
-            times[st] = mean_ms(fw) + mean_ms(bw)
-    full = (H, W, C) == (512, 512, 7)
-    pipe_mult, peak = pipe_products(bf16)
-    if bf16:
-        from nsm_amd.prep import BF16_WINO, BF16_WINO_MIN
-        wino = BF16_WINO and not f16   # f16: direct convolutions only (its parity anchor)
-        work = stage_work(C, H, W, B, bytes_per=2, wino_min=BF16_WINO_MIN if wino else 1 << 30)
-        roof = (wino_f16_roofline(B, H, W, kern_ms, gemm_ms, len(evs)) if wino and gemm_ms
-                else direct_roofline(B, H, W, kern_ms, len(evs), f16))
-        traffic, traffic_src = (load_traffic("traffic_conv6_fwd_gemm_bf16.json" if BF16_WINO
-                                             else "traffic_conv6_fwd_bf16.json")
-                                if B == 64 and full and not f16 else (None, None))
-        tag = f"b{B}_{args.dtype}"
-    else:
-        work = stage_work(C, H, W, B, wino_min=WINOGRAD_MIN_CHANNELS, tile=wino_tile)
-        traffic, traffic_src = (load_traffic("traffic_conv6_fwd_gemm_f32.json") if B == 8 and full
-                                else (None, None))
-        roof = dominant_roofline(B, H, W, kern_ms, gemm_ms, len(evs), wino_tile(1024, H // 8, W // 8))
-        tag = f"b{B}_f32"
-    roof.update({"traffic": traffic, "traffic_source": traffic_src})
-    measured, measured_src = load_stage_pmc(tag) if full else (None, None)
+    def attribution():
+        """--full: the stage table, the roofline object and the VGG probes of
+        attribution steps run after the timed ones."""
+        # attribution steps (not timed): kernel and stage times from HIP events
+        # with the weight gradients on the main stream, the configuration the
+        # per-stage counters are taken in (tools/stage_pmc.py, NSM_STAGE_MARKS),
+        # so each stage's bytes and time describe the same kernels
+        probe_tag = "conv6.conv.0.fwd"
+        nops.PROBES[probe_tag] = []
+        nops.PROBES[probe_tag + ".gemm"] = []
+        for st in STAGES:
+            nops.PROBES[st + ".fwd"] = []
+            nops.PROBES[st + ".bwd"] = []
+        nops.PROBES["vgg.fwd"] = []
+        nops.PROBES["vgg.30"] = []
+        nops.PROBES["vgg.30.gemm"] = []
+        from nsm_amd import unet as nunet
+        side_prev, nunet.WGRAD_STREAM = nunet.WGRAD_STREAM, False
+        try:
+            for _ in range(min(args.steps, 10)):
+                step()
+            torch.cuda.synchronize()
+        finally:
+            nunet.WGRAD_STREAM = side_prev
+        evs = nops.PROBES.pop(probe_tag)
+        kern_ms = mean_ms(evs)
+        gemm_ms = mean_ms(nops.PROBES.pop(probe_tag + ".gemm"))
+        vgg_evs = nops.PROBES.pop("vgg.fwd")
+        vgg30 = nops.PROBES.pop("vgg.30")
+        vgg30_gemm = mean_ms(nops.PROBES.pop("vgg.30.gemm"))
+        times = {}
+        for st in STAGES:
+            fw, bw = nops.PROBES.pop(st + ".fwd"), nops.PROBES.pop(st + ".bwd")
+            if fw and bw:
+                times[st] = mean_ms(fw) + mean_ms(bw)
+        std = (H, W, C) == (512, 512, 7)
+        pipe_mult, peak = pipe_products(bf16)
+        if bf16:
+            from nsm_amd.prep import BF16_WINO, BF16_WINO_MIN
+            wino = BF16_WINO and not f16   # f16: direct convolutions only (its parity anchor)
+            work = stage_work(C, H, W, B, bytes_per=2, wino_min=BF16_WINO_MIN if wino else 1 << 30)
+            roof = (wino_f16_roofline(B, H, W, kern_ms, gemm_ms, len(evs)) if wino and gemm_ms
+                    else direct_roofline(B, H, W, kern_ms, len(evs), f16))
+            traffic, traffic_src = (load_traffic("traffic_conv6_fwd_gemm_bf16.json" if BF16_WINO
+                                                 else "traffic_conv6_fwd_bf16.json")
+                                    if B == 64 and std and not f16 else (None, None))
+            tag = f"b{B}_{args.dtype}"
+        else:
+            work = stage_work(C, H, W, B, wino_min=WINOGRAD_MIN_CHANNELS, tile=wino_tile)
+            traffic, traffic_src = (load_traffic("traffic_conv6_fwd_gemm_f32.json") if B == 8 and std
+                                    else (None, None))
+            roof = dominant_roofline(B, H, W, kern_ms, gemm_ms, len(evs), wino_tile(1024, H // 8, W // 8))
+            tag = f"b{B}_f32"
+        roof.update({"traffic": traffic, "traffic_source": traffic_src})
+        measured, measured_src = load_stage_pmc(tag) if std else (None, None)
+        return ({"stage_cols": STAGE_COLS,
+                 "stages": stage_table(work, times, pipe_mult, peak, measured),
+                 "stage_pmc_source": measured_src, "roofline": roof,
+                 "stage_execution": "eager attribution steps after the timed ones, weight "
+                                    "gradients on the main stream (NSM_WGRAD_STREAM=0: the "
+                                    "configuration of the stage PMC), HIP events per stage"},
+                vgg_evs, vgg30, vgg30_gemm)
+
+    attr, vgg_evs, vgg30, vgg30_gemm = attribution() if full else ({}, [], [], None)
 
     frames = world * B * args.steps
     step_flops = 3 * unet_fwd_flops(C, H, W) * B
@@ -811,17 +887,11 @@ def train_measure(args, world, rank, dev):
         "model_tflops_per_s": round(step_flops * args.steps / elapsed / 1e12 / world, 2),
         "world_size": dist.get_world_size() if dist.is_initialized() else 1,
         "backend": dist.get_backend() if dist.is_initialized() else None,
-        "stage_cols": STAGE_COLS,
-        "stages": stage_table(work, times, pipe_mult, peak, measured),
-        "stage_pmc_source": measured_src,
-        "roofline": roof,
+        **attr,
         "step_execution": ("one hipGraph replay per step (nsm_amd.GraphedTrainStep)"
                            if head_graph and graphed is not None else
                            "eager, back to back (an unchanged main.py loop; the per-rank step "
                            "of data parallelism), weight gradients on the side stream"),
-        "stage_execution": "eager attribution steps after the timed ones, weight gradients on "
-                           "the main stream (NSM_WGRAD_STREAM=0: the configuration of the "
-                           "stage PMC), HIP events per stage",
     }
     if side_elapsed is not None:
         side = {"value": round(world * B * side_steps / side_elapsed, 3),
@@ -865,7 +935,7 @@ def run_infer(args):
     world, rank, dev = init_dist(args)
     res = infer_measure(args, world, rank, dev)
     H, W = (1080, 1920) if args.workload == "infer1080" else (256, 256)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(args.in_ch, H, W, frames=1, reps=3, train=False)
     if rank == 0:
         emit(res, args)
@@ -895,32 +965,40 @@ def infer_measure(args, world, rank, dev):
     torch.cuda.synchronize()
     elapsed = timed(graphed.replay, args.steps, world, dev)
 
-    # kernel/stage timing from eager forwards of the same shape (HIP events
-    # cannot be read back from inside a replayed graph)
-    probe_tag = "conv6.conv.0.fwd"
-    nops.PROBES[probe_tag] = []
-    nops.PROBES[probe_tag + ".gemm"] = []
-    for st in STAGES:
-        nops.PROBES[st + ".fwd"] = []
-    with torch.no_grad():
-        for _ in range(args.steps):
-            model(x)
-    torch.cuda.synchronize()
-    evs = nops.PROBES.pop(probe_tag)
-    gevs = nops.PROBES.pop(probe_tag + ".gemm", [])
-    times = {st: mean_ms(nops.PROBES.pop(st + ".fwd")) for st in STAGES}
-    pipe_mult, peak = pipe_products(bf16)
-    if bf16:
-        from nsm_amd.prep import BF16_WINO, BF16_WINO_EVAL, BF16_WINO_MIN
-        wino = BF16_WINO and BF16_WINO_EVAL and not f16   # bf16 eval: F(4x4) at >= 512 channels
-        work = stage_work(C, H, W, B, bytes_per=2, wino_min=BF16_WINO_MIN if wino else 1 << 30,
-                          passes=1)
-        roof = (wino_f16_roofline(B, H, W, mean_ms(evs), mean_ms(gevs), len(evs)) if wino and gevs
-                else direct_roofline(B, H, W, mean_ms(evs), len(evs), f16))
-    else:
-        work = stage_work(C, H, W, B, wino_min=WINOGRAD_MIN_CHANNELS, tile=wino_tile, passes=1)
-        roof = dominant_roofline(B, H, W, mean_ms(evs), mean_ms(gevs), len(evs), wino_tile(1024, H // 8, W // 8))
-    roof.update({"traffic": None, "traffic_source": None})
+    if getattr(args, "dump_outputs", None) and rank == 0:
+        write_dump(args.dump_outputs, {"out": dump_array(graphed.static_out)})
+
+    def attribution():
+        """--full: the stage table and the roofline object."""
+        # kernel/stage timing from eager forwards of the same shape (HIP events
+        # cannot be read back from inside a replayed graph)
+        probe_tag = "conv6.conv.0.fwd"
+        nops.PROBES[probe_tag] = []
+        nops.PROBES[probe_tag + ".gemm"] = []
+        for st in STAGES:
+            nops.PROBES[st + ".fwd"] = []
+        with torch.no_grad():
+            for _ in range(args.steps):
+                model(x)
+        torch.cuda.synchronize()
+        evs = nops.PROBES.pop(probe_tag)
+        gevs = nops.PROBES.pop(probe_tag + ".gemm", [])
+        times = {st: mean_ms(nops.PROBES.pop(st + ".fwd")) for st in STAGES}
+        pipe_mult, peak = pipe_products(bf16)
+        if bf16:
+            from nsm_amd.prep import BF16_WINO, BF16_WINO_EVAL, BF16_WINO_MIN
+            wino = BF16_WINO and BF16_WINO_EVAL and not f16   # bf16 eval: F(4x4) at >= 512 channels
+            work = stage_work(C, H, W, B, bytes_per=2, wino_min=BF16_WINO_MIN if wino else 1 << 30,
+                              passes=1)
+            roof = (wino_f16_roofline(B, H, W, mean_ms(evs), mean_ms(gevs), len(evs)) if wino and gevs
+                    else direct_roofline(B, H, W, mean_ms(evs), len(evs), f16))
+        else:
+            work = stage_work(C, H, W, B, wino_min=WINOGRAD_MIN_CHANNELS, tile=wino_tile, passes=1)
+            roof = dominant_roofline(B, H, W, mean_ms(evs), mean_ms(gevs), len(evs), wino_tile(1024, H // 8, W // 8))
+        roof.update({"traffic": None, "traffic_source": None})
+        return {"stage_cols": STAGE_COLS, "stages": stage_table(work, times, pipe_mult, peak),
+                "roofline": roof}
+
     frames = world * B * args.steps
     cfg = "configs[4]" if args.workload == "infer1080" else "configs[0]"
     res = {
@@ -941,9 +1019,7 @@ def infer_measure(args, world, rank, dev):
                    "global_batch": world * B, "in_ch": C, "res": [H, W],
                    "parallelism": f"replicas{world}"},
         "model_tflops_per_s": round(unet_fwd_flops(C, H, W) * frames / elapsed / 1e12 / world, 2),
-        "stage_cols": STAGE_COLS,
-        "stages": stage_table(work, times, pipe_mult, peak),
-        "roofline": roof,
+        **(attribution() if getattr(args, "full", False) else {}),
     }
     return res
 
@@ -981,8 +1057,17 @@ def main():
     ap.add_argument("--in-ch", type=int, default=7)
     ap.add_argument("--res", type=int, default=512)
     ap.add_argument("--workload", choices=["train", "infer1080", "infer256"], default="train")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the other execution of the step (graph / eager), "
+                         "the stage table and roofline object, the secondary configs, the CPU "
+                         "baselines")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy "
+                         "(float32; arrays above 2^21 elements as a fixed seeded sample). Train: "
+                         "loss, params, buffers and, from the eager step, out and x_grad; with "
+                         "--full they are those of the execution timed first")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="train, N=1: skip the other configs measured after the headline one")
+                    help="--full, train: skip the other configs measured after the headline one")
     ap.add_argument("--dtype", choices=["f32", "bf16", "f16"], default="f32",
                     help="bf16: configs[2] (use --batch 64); f16: the reference's fp16-autocast "
                          "mode (train only)")
@@ -997,6 +1082,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU/gloo launcher check with a stand-in step (no GPU, not a measurement)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     args.batch = args.batch or (8 if args.workload == "train" else 1)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no torchrun: one worker process per GPU, spawned before anything

@@ -22,7 +22,7 @@ def _run(args, env=None):
 
 @pytest.mark.timeout(300)
 def test_bench_spawns_two_ranks():
-    r = _run(["--gpus", "2", "--steps", "5", "--warmup", "1"])
+    r = _run(["--gpus", "2", "--steps", "5", "--warmup", "1", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(line) == 1
@@ -37,3 +37,36 @@ def test_bench_spawns_two_ranks():
 def test_bench_rejects_world_mismatch():
     r = _run(["--gpus", "1"], env={"WORLD_SIZE": "2"})
     assert r.returncode != 0 and "WORLD_SIZE=2" in (r.stderr + r.stdout)
+
+
+def test_plain_dry_run_plans_the_headline_only_and_dumps(tmp_path):
+    """Without --full the run measures the headline alone; --dump-outputs
+    writes float32 .npy files, identical from run to run."""
+    import numpy as np
+    outs = []
+    for d in ("a", "b"):
+        r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1",
+                  "--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        assert [w["role"] for w in line["workloads"]] == ["headline"]
+        assert line["steps"] == 3 and line["ms_per_step"] >= 0
+        outs.append(np.load(tmp_path / d / "buf.npy"))
+    assert outs[0].dtype == np.float32 and np.array_equal(outs[0], outs[1])
+
+
+def test_dump_array_samples_large_outputs_at_fixed_positions():
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    small = torch.arange(12, dtype=torch.bfloat16).reshape(3, 4)
+    a = bench.dump_array(small)
+    assert a.dtype == np.float32 and a.shape == (3, 4)
+    assert bench.dump_array(small.double()).dtype == np.float64
+    n = 3 * bench.DUMP_MAX_ELEMS + 7
+    big = torch.arange(n, dtype=torch.float32).reshape(-1, 1)   # n < 2^24: exact
+    s1, s2 = bench.dump_array(big), bench.dump_array(big.clone())
+    assert s1.shape == (bench.DUMP_MAX_ELEMS,) and s1.nbytes * 5 <= 64e6
+    assert np.array_equal(s1, s2) and np.all(np.diff(s1) >= 0)
+    assert s1.min() >= 0 and s1.max() < n and s1.max() > 0.99 * n

@@ -9,7 +9,7 @@ REPS=${REPS:-2}
 for rep in $(seq 1 "$REPS"); do
   for arm in $ARMS; do
     envs=$(echo "$arm" | tr ',' ' '); [ "$arm" = "-" ] && envs="NSM_AB_BASE=1"
-    env $envs timeout -k 10 300 python bench.py --steps ${STEPS:-30} --warmup 5 --no-secondary \
+    env $envs timeout -k 10 300 python bench.py --full --steps ${STEPS:-30} --warmup 5 --no-secondary \
         --no-cpu-baseline $ARGS > $O/b.log 2>&1 || exit $?
     line="$arm $(python3 -c "import json,sys; d=json.loads([l for l in open('$O/b.log') if l.startswith('{')][-1]); print(d['value'], d['ms_per_step'])")"
     echo "$line" | tee -a $O/res.log

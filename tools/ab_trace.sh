@@ -11,7 +11,7 @@ for v in "${VS[@]}"; do
   i=$((i+1))
   rm -rf $O/raw$i
   env $v timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/raw$i -o run -- \
-    python3 bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-secondary ${CFG:-} > $O/bench$i.log 2>&1 || { echo "variant $v failed"; tail -5 $O/bench$i.log; exit 1; }
+    python3 bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-secondary ${CFG:-} > $O/bench$i.log 2>&1 || { echo "variant $v failed"; tail -5 $O/bench$i.log; exit 1; }
   python3 tools/step_timeline.py "$(find $O/raw$i -name run_kernel_trace.csv -print -quit)" > $O/tl$i.txt
   rm -rf $O/raw$i
   echo "== $v  $(grep -o '"value":[0-9.]*' $O/bench$i.log | head -1)  $(grep '^kernels' $O/tl$i.txt)"

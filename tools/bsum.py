@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One-line summaries of bench.py JSON logs: python tools/bsum.py log [log ...]"""
+"""One-line summaries of `bench.py --full` JSON logs: python tools/bsum.py log [log ...]"""
 import json
 import sys
 

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 O=gpurun_out/dpq; mkdir -p $O
 for f in "" "--force-dp"; do
   rm -rf $O/raw
-  timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/raw -o run -- python3 bench.py --steps 5 --warmup 3 --no-secondary --no-cpu-baseline $f > $O/log 2>&1 || { tail -5 $O/log; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/raw -o run -- python3 bench.py --full --steps 5 --warmup 3 --no-secondary --no-cpu-baseline $f > $O/log 2>&1 || { tail -5 $O/log; exit 1; }
   echo "== ${f:-plain}"
   python3 - "$(find $O/raw -name run_kernel_trace.csv -print -quit)" <<'PY'
 import csv, sys, collections

@@ -104,7 +104,8 @@ def main():
         report = []
         for kw in (dict(dtype="f32", batch=8, steps=20, warmup=5),
                    dict(dtype="bf16", batch=64, steps=10, warmup=3)):
-            args = argparse.Namespace(in_ch=7, res=512, vgg=False, workload="train", **kw)
+            args = argparse.Namespace(in_ch=7, res=512, vgg=False, workload="train", full=True,
+                                      **kw)
             torch.cuda.empty_cache()
             rec["all"] = []
             real_bwd2 = unet._block_bwd

@@ -10,7 +10,7 @@ i=0
 for P in "$P1" "$P2"; do
   i=$((i+1)); rm -rf $O/raw$i
   timeout -s KILL 150 rocprofv3 --pmc $P --kernel-include-regex "$PAT" --output-format csv -d $O/raw$i -o run -- \
-    python3 bench.py --dtype bf16 --batch 64 --steps 2 --warmup 1 --no-secondary --no-cpu-baseline > $O/bench$i.log 2>&1
+    python3 bench.py --full --dtype bf16 --batch 64 --steps 2 --warmup 1 --no-secondary --no-cpu-baseline > $O/bench$i.log 2>&1
   python3 tools/pmc_disp.py "$(find $O/raw$i -name run_counter_collection.csv -print -quit)" "$PAT" 60 > $O/disp$i.txt
   rm -rf $O/raw$i
 done

@@ -3,7 +3,7 @@ set -euo pipefail
 OUT=gpurun_out/pmc_step
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-B="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary ${CFG:-}"
+B="python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-secondary ${CFG:-}"
 timeout -s KILL 240 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU \
   SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_WAIT_ANY SQ_INSTS_VMEM GRBM_GUI_ACTIVE \
   --output-format csv -d "$OUT/r1" -o run -- $B > "$OUT/b1.log" 2>&1

@@ -19,7 +19,7 @@ OUT=gpurun_out/prof_$R
 mkdir -p "$OUT" "profiles/$R"
 export TMPDIR=/tmp
 f() { find "$OUT/$1" -name "$2" -print -quit; }
-BENCH="python3 bench.py --no-cpu-baseline --no-secondary"
+BENCH="python3 bench.py --full --no-cpu-baseline --no-secondary"
 pmc() {  # tag name counters... (marked run, kernel trace only besides the counters)
   local tag=$1 name=$2; shift 2
   NSM_STAGE_MARKS=1 timeout -s KILL 300 rocprofv3 --pmc "$@" --output-format csv -d "$OUT/${name}_$tag" -o run -- \
