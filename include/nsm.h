@@ -599,6 +599,17 @@ int nsm_clip_coef(const float* sumsq, float inv_world, float max_norm, float* co
 int nsm_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
                    float beta2, float eps, float weight_decay, int step, const float* gcoef,
                    void* stream);
+/* main.py:953 / :957: the other two optimizer settings, same conventions (host
+ * step count >= 1, optional device clip coefficient gcoef).
+ * nsm_adam_step: torch.optim.Adam, L2 weight decay (g += wd*p before the moments).
+ * nsm_sgd_step: torch.optim.SGD, dampening 0, no Nesterov: g += wd*p; buf = g
+ *   when step == 1, else buf = momentum*buf + g; p -= lr*buf. momentum == 0 is
+ *   p -= lr*g and buf may be NULL. */
+int nsm_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
+                  float beta2, float eps, float weight_decay, int step, const float* gcoef,
+                  void* stream);
+int nsm_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr, float momentum,
+                 float weight_decay, int step, const float* gcoef, void* stream);
 
 /* ---- the reference's full step tail (main.py:287-423), no host sync ----------
  * The gradient is one flat fp32 buffer of the module's parameters in order;
@@ -622,7 +633,13 @@ int nsm_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, floa
  *   calls; `step` holds two ints). workspace: nsm_tail_ws_bytes().
  * nsm_adamw_tail: torch.optim.AdamW step (main.py:421, hyper-parameters
  *   main.py:955) with g scaled by seg_coef; a no-op when flags[0] is set; the
- *   bias corrections use the device step count. */
+ *   bias corrections use the device step count.
+ * nsm_adam_tail: the same for torch.optim.Adam (main.py:953; L2 weight decay).
+ * nsm_sgd_tail: the same for torch.optim.SGD with momentum (main.py:957): the
+ *   momentum buffer is set to the gradient on the first step taken (step[0]
+ *   == 1, so a skipped first step leaves the next one to initialise it) and is
+ *   momentum*buf + g afterwards; momentum == 0 touches no buffer (buf may be
+ *   NULL). */
 int64_t nsm_tail_chunk(void);
 int nsm_tail_plan(const int64_t* seg_off, int nseg, int* blk_seg, int64_t* blk_lo,
                   int64_t* blk_hi, int* seg_blk, int cap);
@@ -636,6 +653,13 @@ int nsm_adamw_tail(float* p, const float* g, float* m, float* v, const int* blk_
                    const int64_t* blk_lo, const int64_t* blk_hi, int nblk, const float* seg_coef,
                    const int* flags, const int* step, double lr, double beta1, double beta2,
                    double eps, double weight_decay, void* stream);
+int nsm_adam_tail(float* p, const float* g, float* m, float* v, const int* blk_seg,
+                  const int64_t* blk_lo, const int64_t* blk_hi, int nblk, const float* seg_coef,
+                  const int* flags, const int* step, double lr, double beta1, double beta2,
+                  double eps, double weight_decay, void* stream);
+int nsm_sgd_tail(float* p, const float* g, float* buf, const int* blk_seg, const int64_t* blk_lo,
+                 const int64_t* blk_hi, int nblk, const float* seg_coef, const int* flags,
+                 const int* step, double lr, double momentum, double weight_decay, void* stream);
 
 /* ---- drop-in surface helpers ---------------------------------------------------
  * NCHW fp32 <-> NHWC [B*H*W][cp] (dtype NSM_F32 / NSM_BF16) for a standalone

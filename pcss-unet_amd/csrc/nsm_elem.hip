@@ -1906,6 +1906,54 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
   }
 }
 
+// torch.optim.Adam (single-tensor path, L2 weight decay): g += wd*p, then the
+// moments and the update of adamw_kernel without the decoupled decay. Every
+// rounding of torch's op sequence is kept (no FMA contraction).
+__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
+                            float* __restrict__ m, float* __restrict__ v, int64_t n, float wd,
+                            float beta1, float beta2, float eps, float step_size, float bc2_sqrt,
+                            const float* __restrict__ gcoef) {
+#pragma clang fp contract(off)
+  const float gc = gcoef ? gcoef[0] : 1.f;
+  const float w1 = 1.f - beta1, w2 = 1.f - beta2;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    float pi = p[i];
+    float gi = g[i] * gc;
+    gi = gi + wd * pi;
+    float mi = m[i];
+    mi = mi + w1 * (gi - mi);
+    float vi = v[i] * beta2;
+    vi = vi + (w2 * gi) * gi;
+    float denom = sqrtf(vi) / bc2_sqrt + eps;
+    pi = pi - step_size * (mi / denom);
+    p[i] = pi;
+    m[i] = mi;
+    v[i] = vi;
+  }
+}
+
+// torch.optim.SGD (dampening 0, no Nesterov): g += wd*p; buf = g on the first
+// step, else buf = mu*buf + g; p -= lr*buf. MOMENTUM = false: p -= lr*g, no buffer.
+template <bool MOMENTUM>
+__global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g,
+                           float* __restrict__ buf, int64_t n, float lr, float momentum, float wd,
+                           int first, const float* __restrict__ gcoef) {
+#pragma clang fp contract(off)
+  const float gc = gcoef ? gcoef[0] : 1.f;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    float pi = p[i];
+    float gi = g[i] * gc;
+    gi = gi + wd * pi;
+    if (MOMENTUM) {
+      if (!first) gi = buf[i] * momentum + gi;
+      buf[i] = gi;
+    }
+    p[i] = pi - lr * gi;
+  }
+}
+
 // grid for the xcd_block() kernels: a multiple of 8 blocks, <= 2048
 static inline int xcd_grid(long long work) {
   long long g = (work + 255) / 256;
@@ -2762,6 +2810,34 @@ extern "C" int nsm_adamw_step(float* p, const float* g, float* m, float* v, int6
   hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), p, g, m, v,
                      n, decay, beta1, beta2, eps, step_size, bc2_sqrt, gcoef);
   NSM_LAUNCH_CHECK("adamw");
+  return 0;
+}
+
+extern "C" int nsm_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr,
+                             float beta1, float beta2, float eps, float weight_decay, int step,
+                             const float* gcoef, void* stream) {
+  NSM_CHECK_ARG(p && g && m && v && n > 0 && step >= 1, "adam: bad args");
+  double bc1 = 1.0 - pow((double)beta1, step);
+  double bc2 = 1.0 - pow((double)beta2, step);
+  float step_size = (float)(lr / bc1);
+  float bc2_sqrt = (float)sqrt(bc2);
+  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), p, g, m, v,
+                     n, weight_decay, beta1, beta2, eps, step_size, bc2_sqrt, gcoef);
+  NSM_LAUNCH_CHECK("adam");
+  return 0;
+}
+
+extern "C" int nsm_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr,
+                            float momentum, float weight_decay, int step, const float* gcoef,
+                            void* stream) {
+  NSM_CHECK_ARG(p && g && n > 0 && step >= 1 && (buf || momentum == 0.f), "sgd: bad args");
+  if (momentum != 0.f)
+    hipLaunchKernelGGL(sgd_kernel<true>, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), p, g,
+                       buf, n, lr, momentum, weight_decay, step == 1 ? 1 : 0, gcoef);
+  else
+    hipLaunchKernelGGL(sgd_kernel<false>, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), p, g,
+                       (float*)nullptr, n, lr, 0.f, weight_decay, 0, gcoef);
+  NSM_LAUNCH_CHECK("sgd");
   return 0;
 }
 

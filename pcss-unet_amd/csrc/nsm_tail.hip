@@ -2,7 +2,8 @@
 // synchronisation: gradient sanitising (NaN/Inf census, >20 % skip, repair),
 // the per-parameter pre-unscale clip to 1000*scale, the per-parameter 1e5 skip /
 // 1e3 rescale, clip_grad_norm_(max_norm), the post-clip max-norm > 10 skip, and
-// an AdamW step that honours the device skip flag.
+// an AdamW (or Adam, or SGD: main.py:952-957) step that honours the device skip
+// flag.
 //
 // The gradient is ONE flat fp32 buffer holding the module's parameters in
 // order; `seg_off[nseg+1]` delimits the parameters ("segments"). Work is cut
@@ -450,6 +451,76 @@ __global__ void __launch_bounds__(TAIL_THREADS) tail_adamw_kernel(
   }
 }
 
+// ---- K5': Adam (torch.optim.Adam, single-tensor path, L2 weight decay) --------
+// g = ((g*f1)*f2)*c (or 0 if zeroed); g += wd*p; m = lerp(m, g, 1-b1);
+// v = v*b2 + (1-b2)*g*g; p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps).
+// 28 B per element, like AdamW: p, m, v read and written, g read.
+__global__ void __launch_bounds__(TAIL_THREADS) tail_adam_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+    float* __restrict__ v, const int* __restrict__ blk_seg, const int64_t* __restrict__ blk_lo,
+    const int64_t* __restrict__ blk_hi, const float* __restrict__ seg_coef,
+    const int* __restrict__ flags, const int* __restrict__ step, double lr, double beta1,
+    double beta2, float eps, double weight_decay) {
+  if (flags[0]) return;  // skipped step
+  const int b = blockIdx.x, sgi = blk_seg[b];
+  const int64_t lo = blk_lo[b], hi = blk_hi[b];
+  const float f1 = seg_coef[4 * sgi + 0], f2 = seg_coef[4 * sgi + 1], c = seg_coef[4 * sgi + 2];
+  const bool zero = seg_coef[4 * sgi + 3] != 0.f;
+  const double t = (double)step[0];
+  const double bc1 = 1.0 - pow(beta1, t), bc2 = 1.0 - pow(beta2, t);
+  const float wd = (float)weight_decay;
+  const float w1 = (float)(1.0 - beta1), b2 = (float)beta2, w2 = (float)(1.0 - beta2);
+  const float step_size = (float)(lr / bc1), bc2s = (float)sqrt(bc2);
+  for (int64_t i = lo + threadIdx.x; i < hi; i += TAIL_THREADS) {
+    float gi = 0.f;
+    if (!zero) gi = ((g[i] * f1) * f2) * c;
+    float pi = p[i];
+    gi = gi + wd * pi;  // grad.add(param, alpha=weight_decay)
+    float mi = m[i];
+    mi = mi + w1 * (gi - mi);
+    float vi = v[i] * b2;
+    vi = vi + (w2 * gi) * gi;
+    const float denom = sqrtf(vi) / bc2s + eps;
+    pi = pi - step_size * (mi / denom);
+    p[i] = pi;
+    m[i] = mi;
+    v[i] = vi;
+  }
+}
+
+// ---- K5'': SGD (torch.optim.SGD, momentum, dampening 0, no Nesterov) ----------
+// g = ((g*f1)*f2)*c (or 0 if zeroed); g += wd*p; buf = g on the first step
+// taken (step[0] == 1: torch clones the first stepped gradient into the
+// buffer, and a skipped step does not advance step[0]), else buf = mu*buf + g;
+// p -= lr*buf. 20 B per element (p read and written, buf read and written, g
+// read; the first step does not read buf). MOMENTUM = false is p -= lr*g with
+// no buffer at all: 12 B per element.
+template <bool MOMENTUM>
+__global__ void __launch_bounds__(TAIL_THREADS) tail_sgd_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+    const int* __restrict__ blk_seg, const int64_t* __restrict__ blk_lo,
+    const int64_t* __restrict__ blk_hi, const float* __restrict__ seg_coef,
+    const int* __restrict__ flags, const int* __restrict__ step, float lr, float momentum,
+    float weight_decay) {
+  if (flags[0]) return;  // skipped step
+  const int b = blockIdx.x, sgi = blk_seg[b];
+  const int64_t lo = blk_lo[b], hi = blk_hi[b];
+  const float f1 = seg_coef[4 * sgi + 0], f2 = seg_coef[4 * sgi + 1], c = seg_coef[4 * sgi + 2];
+  const bool zero = seg_coef[4 * sgi + 3] != 0.f;
+  const bool first = step[0] == 1;  // uniform across the grid
+  for (int64_t i = lo + threadIdx.x; i < hi; i += TAIL_THREADS) {
+    float gi = 0.f;
+    if (!zero) gi = ((g[i] * f1) * f2) * c;
+    float pi = p[i];
+    gi = gi + weight_decay * pi;
+    if (MOMENTUM) {
+      if (!first) gi = buf[i] * momentum + gi;  // buf.mul_(momentum).add_(grad)
+      buf[i] = gi;
+    }
+    p[i] = pi - lr * gi;
+  }
+}
+
 }  // namespace nsm
 
 using namespace nsm;
@@ -520,5 +591,39 @@ extern "C" int nsm_adamw_tail(float* p, const float* g, float* m, float* v, cons
                      m, v, blk_seg, blk_lo, blk_hi, seg_coef, flags, step, lr, beta1, beta2,
                      (float)eps, weight_decay);
   NSM_LAUNCH_CHECK("adamw_tail");
+  return 0;
+}
+
+extern "C" int nsm_adam_tail(float* p, const float* g, float* m, float* v, const int* blk_seg,
+                             const int64_t* blk_lo, const int64_t* blk_hi, int nblk,
+                             const float* seg_coef, const int* flags, const int* step, double lr,
+                             double beta1, double beta2, double eps, double weight_decay,
+                             void* stream) {
+  NSM_CHECK_ARG(p && g && m && v && blk_seg && blk_lo && blk_hi && seg_coef && flags && step &&
+                    nblk > 0,
+                "adam_tail: bad args");
+  hipLaunchKernelGGL(tail_adam_kernel, dim3(nblk), dim3(TAIL_THREADS), 0, as_stream(stream), p, g,
+                     m, v, blk_seg, blk_lo, blk_hi, seg_coef, flags, step, lr, beta1, beta2,
+                     (float)eps, weight_decay);
+  NSM_LAUNCH_CHECK("adam_tail");
+  return 0;
+}
+
+extern "C" int nsm_sgd_tail(float* p, const float* g, float* buf, const int* blk_seg,
+                            const int64_t* blk_lo, const int64_t* blk_hi, int nblk,
+                            const float* seg_coef, const int* flags, const int* step, double lr,
+                            double momentum, double weight_decay, void* stream) {
+  NSM_CHECK_ARG(p && g && blk_seg && blk_lo && blk_hi && seg_coef && flags && step && nblk > 0 &&
+                    (buf || momentum == 0.0),
+                "sgd_tail: bad args");
+  if (momentum != 0.0)
+    hipLaunchKernelGGL(tail_sgd_kernel<true>, dim3(nblk), dim3(TAIL_THREADS), 0, as_stream(stream),
+                       p, g, buf, blk_seg, blk_lo, blk_hi, seg_coef, flags, step, (float)lr,
+                       (float)momentum, (float)weight_decay);
+  else
+    hipLaunchKernelGGL(tail_sgd_kernel<false>, dim3(nblk), dim3(TAIL_THREADS), 0,
+                       as_stream(stream), p, g, (float*)nullptr, blk_seg, blk_lo, blk_hi, seg_coef,
+                       flags, step, (float)lr, 0.f, (float)weight_decay);
+  NSM_LAUNCH_CHECK("sgd_tail");
   return 0;
 }

@@ -128,6 +128,8 @@ _SIGS = {
     "nsm_sumsq": (I, [P, L, P, P, P]),
     "nsm_clip_coef": (I, [P, F, F, P, P]),
     "nsm_adamw_step": (I, [P, P, P, P, L, F, F, F, F, F, I, P, P]),
+    "nsm_adam_step": (I, [P, P, P, P, L, F, F, F, F, F, I, P, P]),
+    "nsm_sgd_step": (I, [P, P, P, L, F, F, F, I, P, P]),
     "nsm_vgg_prep": (I, [P, P, I, I, I, F, F, P, P]),
     "nsm_npy_info": (I, [ctypes.c_char_p, P, I, P, P, P]),
     "nsm_loader_create": (P, [ctypes.c_char_p, ctypes.c_char_p, I, I, I, I, I]),
@@ -151,6 +153,8 @@ _SIGS = {
     "nsm_tail_ws_bytes": (Z, [I, I]),
     "nsm_grad_tail": (I, [P, I, P, P, P, P, P, I, F, F, F, P, U64, P, Z, P, P, P, P, P]),
     "nsm_adamw_tail": (I, [P, P, P, P, P, P, P, I, P, P, P, D, D, D, D, D, P]),
+    "nsm_adam_tail": (I, [P, P, P, P, P, P, P, I, P, P, P, D, D, D, D, D, P]),
+    "nsm_sgd_tail": (I, [P, P, P, P, P, P, I, P, P, P, D, D, D, P]),
     "nsm_nchw_to_nhwc": (I, [P, I, I, I, I, P, I, I, I, P]),
     "nsm_nhwc_to_nchw": (I, [P, I, I, I, I, I, P, I, P]),
     "nsm_range_flag": (I, [P, L, F, F, P, P]),

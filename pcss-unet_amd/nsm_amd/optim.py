@@ -25,6 +25,13 @@ named_parameters are unchanged). The Unet backward writes all 66 gradients
 into one flat buffer too, so the DP exchange is one all-reduce of 60 MiB.
 `state_dict()` / `load_state_dict()` use torch.optim.AdamW's format, so
 main.py's `optimizer_state_dict` checkpoints interchange.
+
+main.py:952-957 builds Adam, AdamW or (for any other `optimizer_type`) SGD with
+momentum. `FlatAdam` and `FlatSGD` are the other two on the same flat buffer
+and the same device tail: everything up to the update (`nsm_grad_tail`) is
+shared, only the last kernel differs (`nsm_adam_tail` / `nsm_sgd_tail`), and
+their checkpoints are torch.optim.Adam's / torch.optim.SGD's.
+`make_optimizer(params, optimizer_type, lr)` is that three-way block.
 """
 import math
 import os
@@ -138,13 +145,25 @@ def _bump(params):
             torch.autograd.graph.increment_version(p)
 
 
-class FlatAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=7e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-3,
-                 max_grad_norm=None, world_size=1, sanitize=False, grad_scale=1.0, seed=None):
+class _FlatOptimizer(torch.optim.Optimizer):
+    """What FlatAdamW, FlatAdam and FlatSGD share: the parameters re-homed into
+    one flat fp32 buffer, the block plan and workspace of the device tail, the
+    DP averaging (inv_world) and the rank-0 repair seed, the max_norm schedule,
+    the `nsm_grad_tail` call and the inspection helpers. A subclass allocates
+    its state (`_alloc_state`), launches its update kernel (`_tail_update` after
+    nsm_grad_tail, `_plain_update` for sanitize=False) and names the torch
+    optimizer whose checkpoint format it reads and writes (`_TORCH`)."""
+    _TORCH = None
+    # group options the kernels do not implement: {key: the only value accepted}
+    _REFUSED = {}
+
+    def __init__(self, params, defaults, max_grad_norm=None, world_size=1, sanitize=False,
+                 grad_scale=1.0, seed=None):
         params = list(params)
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        super().__init__(params, defaults)
         if len(self.param_groups) != 1:
-            raise ValueError("FlatAdamW supports one param group")
+            raise ValueError(f"{type(self).__name__} supports one param group")
+        params = self.param_groups[0]["params"]
         dev = params[0].device
         total = sum(p.numel() for p in params)
         self.flat = torch.empty(total, dtype=torch.float32, device=dev)
@@ -157,8 +176,7 @@ class FlatAdamW(torch.optim.Optimizer):
                 p.data = self.flat[off:off + n].view_as(p)
                 off += n
                 offs.append(off)
-        self.exp_avg = torch.zeros_like(self.flat)
-        self.exp_avg_sq = torch.zeros_like(self.flat)
+        self._alloc_state()
         self.max_grad_norm = max_grad_norm
         self.world_size = world_size
         self.inv_world = 1.0 / world_size
@@ -169,7 +187,7 @@ class FlatAdamW(torch.optim.Optimizer):
         self._partial = torch.empty(nb, dtype=torch.float32, device=dev)
         self._sumsq = torch.empty((), dtype=torch.float32, device=dev)
         self._coef = torch.empty((), dtype=torch.float32, device=dev)
-        # device state of the reference tail: [AdamW steps taken, tail calls]
+        # device state of the reference tail: [optimizer steps taken, tail calls]
         self._step_dev = torch.zeros(2, dtype=torch.int32, device=dev)
         self.flags = torch.zeros(8, dtype=torch.int32, device=dev)
         self.stat = torch.zeros(4, dtype=torch.float32, device=dev)
@@ -209,6 +227,40 @@ class FlatAdamW(torch.optim.Optimizer):
         self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         self._seg_coef = torch.zeros(4 * nseg, dtype=torch.float32, device=dev)
 
+    # ---- what a subclass provides --------------------------------------------
+    def _alloc_state(self):
+        raise NotImplementedError
+
+    def _tail_update(self, g, grp, st):
+        """The update kernel after nsm_grad_tail (reads flags / seg_coef / the
+        device step count)."""
+        raise NotImplementedError
+
+    def _plain_update(self, g, n, grp, coef, st):
+        """The sanitize=False update (host step count self.step_count)."""
+        raise NotImplementedError
+
+    def _moments(self):
+        """The flat state tensors the update kernel writes."""
+        raise NotImplementedError
+
+    def _hyper_keys(self):
+        raise NotImplementedError
+
+    # ---- what GraphedTrainStep needs -----------------------------------------
+    def step_state(self):
+        """Every tensor a step writes besides its scratch: the flat parameters,
+        the optimizer's flat state, the tail's device counters and flags."""
+        return [self.flat] + self._moments() + [self._step_dev, self.flags, self.stat]
+
+    def step_hyper(self):
+        """The hyper-parameters a step passes as kernel arguments (a captured
+        graph freezes them: a change needs a new capture)."""
+        g = self.param_groups[0]
+        vals = tuple(tuple(g[k]) if isinstance(g[k], (tuple, list)) else float(g[k])
+                     for k in self._hyper_keys())
+        return vals + (self.max_grad_norm, self.grad_scale)
+
     # main.py:357-358
     def set_epoch(self, epoch, num_epochs):
         """Apply the reference's max_norm schedule for `epoch` of `num_epochs`."""
@@ -225,7 +277,6 @@ class FlatAdamW(torch.optim.Optimizer):
             g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1)
                            for p in params])
         grp = self.param_groups[0]
-        b1, b2 = grp["betas"]
         n = self.flat.numel()
         st = stream()
         if self.sanitize:
@@ -235,10 +286,7 @@ class FlatAdamW(torch.optim.Optimizer):
                  self.inv_world, self.grad_scale, mx, ptr(noise), self.seed, ptr(self._ws),
                  self._ws.numel(), ptr(self._seg_coef), ptr(self.stat), ptr(self.flags),
                  ptr(self._step_dev), st)
-            call("nsm_adamw_tail", ptr(self.flat), ptr(g), ptr(self.exp_avg), ptr(self.exp_avg_sq),
-                 ptr(self._blk_seg), ptr(self._blk_lo), ptr(self._blk_hi), self._nblk,
-                 ptr(self._seg_coef), ptr(self.flags), ptr(self._step_dev), float(grp["lr"]),
-                 float(b1), float(b2), float(grp["eps"]), float(grp["weight_decay"]), st)
+            self._tail_update(g, grp, st)
             _bump(params)
             return None
         self.step_count += 1
@@ -248,9 +296,7 @@ class FlatAdamW(torch.optim.Optimizer):
             mx = float(self.max_grad_norm) if self.max_grad_norm is not None else float("inf")
             call("nsm_clip_coef", ptr(self._sumsq), self.inv_world, mx, ptr(self._coef), st)
             coef = self._coef
-        call("nsm_adamw_step", ptr(self.flat), ptr(g), ptr(self.exp_avg), ptr(self.exp_avg_sq), n,
-             float(grp["lr"]), float(b1), float(b2), float(grp["eps"]), float(grp["weight_decay"]),
-             self.step_count, ptr(coef), st)
+        self._plain_update(g, n, grp, coef, st)
         _bump(params)
         return None
 
@@ -270,12 +316,65 @@ class FlatAdamW(torch.optim.Optimizer):
         d.update(total_norm=s[0], clip_coef=s[1], max_norm=s[2], max_clipped_norm=s[3])
         return d
 
-    # ---- torch.optim.AdamW-compatible checkpoint format ----------------------
+    # ---- the torch twin's checkpoint format -----------------------------------
     def _torch_group_defaults(self):
-        ref = torch.optim.AdamW([torch.zeros(1)])
+        ref = self._TORCH([torch.zeros(1)], lr=1e-3)
         d = dict(ref.defaults)
         d.update({k: v for k, v in self.param_groups[0].items() if k != "params"})
         return d
+
+    def _check_refused(self, opts):
+        for k, ok in self._REFUSED.items():
+            if k in opts and opts[k] != ok:
+                raise ValueError(f"{type(self).__name__} does not implement {k}={opts[k]!r}")
+
+    def _load_group(self, sd, keys):
+        """Check a torch state_dict's single group against ours and take its
+        hyper-parameters; returns the group."""
+        params = self.param_groups[0]["params"]
+        groups = sd["param_groups"]
+        if len(groups) != 1 or len(groups[0]["params"]) != len(params):
+            raise ValueError(f"state_dict does not match {type(self).__name__}'s single "
+                             "parameter group")
+        grp = groups[0]
+        self._check_refused(grp)
+        for k in keys + ("initial_lr",):
+            if k in grp:
+                self.param_groups[0][k] = grp[k]
+        return grp
+
+    def _set_steps(self, s):
+        self.step_count = s
+        self._step_dev[0] = s
+
+
+class _FlatAdamFamily(_FlatOptimizer):
+    """Adam-type state: two flat moments and one step count, checkpointed as
+    torch's `step` / `exp_avg` / `exp_avg_sq` per parameter."""
+    _TAIL = _STEP = None
+
+    def _alloc_state(self):
+        self.exp_avg = torch.zeros_like(self.flat)
+        self.exp_avg_sq = torch.zeros_like(self.flat)
+
+    def _moments(self):
+        return [self.exp_avg, self.exp_avg_sq]
+
+    def _hyper_keys(self):
+        return ("lr", "betas", "eps", "weight_decay")
+
+    def _tail_update(self, g, grp, st):
+        b1, b2 = grp["betas"]
+        call(self._TAIL, ptr(self.flat), ptr(g), ptr(self.exp_avg), ptr(self.exp_avg_sq),
+             ptr(self._blk_seg), ptr(self._blk_lo), ptr(self._blk_hi), self._nblk,
+             ptr(self._seg_coef), ptr(self.flags), ptr(self._step_dev), float(grp["lr"]),
+             float(b1), float(b2), float(grp["eps"]), float(grp["weight_decay"]), st)
+
+    def _plain_update(self, g, n, grp, coef, st):
+        b1, b2 = grp["betas"]
+        call(self._STEP, ptr(self.flat), ptr(g), ptr(self.exp_avg), ptr(self.exp_avg_sq), n,
+             float(grp["lr"]), float(b1), float(b2), float(grp["eps"]), float(grp["weight_decay"]),
+             self.step_count, ptr(coef), st)
 
     def state_dict(self):
         params = self.param_groups[0]["params"]
@@ -294,16 +393,7 @@ class FlatAdamW(torch.optim.Optimizer):
 
     def load_state_dict(self, sd):
         params = self.param_groups[0]["params"]
-        groups = sd["param_groups"]
-        if len(groups) != 1 or len(groups[0]["params"]) != len(params):
-            raise ValueError("state_dict does not match FlatAdamW's single parameter group")
-        grp = groups[0]
-        for k in ("lr", "betas", "eps", "weight_decay"):
-            if k in grp:
-                self.param_groups[0][k] = grp[k]
-        for k in ("initial_lr",):
-            if k in grp:
-                self.param_groups[0][k] = grp[k]
+        grp = self._load_group(sd, ("lr", "betas", "eps", "weight_decay"))
         steps = set()
         off = 0
         with torch.no_grad():
@@ -320,7 +410,140 @@ class FlatAdamW(torch.optim.Optimizer):
                     steps.add(0)
                 off += n
         if len(steps) != 1:
-            raise ValueError(f"FlatAdamW keeps one step count; checkpoint has {sorted(steps)}")
-        s = steps.pop()
-        self.step_count = s
-        self._step_dev[0] = s
+            raise ValueError(f"{type(self).__name__} keeps one step count; checkpoint has "
+                             f"{sorted(steps)}")
+        self._set_steps(steps.pop())
+
+
+class FlatAdamW(_FlatAdamFamily):
+    """main.py:955 `optim.AdamW(lr, weight_decay=1e-3)` (decoupled weight decay)."""
+    _TORCH = torch.optim.AdamW
+    _TAIL, _STEP = "nsm_adamw_tail", "nsm_adamw_step"
+
+    def __init__(self, params, lr=7e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-3,
+                 max_grad_norm=None, world_size=1, sanitize=False, grad_scale=1.0, seed=None):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay),
+                         max_grad_norm, world_size, sanitize, grad_scale, seed)
+
+
+class FlatAdam(_FlatAdamFamily):
+    """main.py:953 `optim.Adam(lr, weight_decay=1e-4)`: L2 weight decay added to
+    the gradient before the moments (torch.optim.Adam's single-tensor path)."""
+    _TORCH = torch.optim.Adam
+    _TAIL, _STEP = "nsm_adam_tail", "nsm_adam_step"
+    _REFUSED = {"amsgrad": False, "maximize": False}
+
+    def __init__(self, params, lr=7e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-4,
+                 max_grad_norm=None, world_size=1, sanitize=False, grad_scale=1.0, seed=None,
+                 amsgrad=False, maximize=False):
+        self._check_refused(dict(amsgrad=amsgrad, maximize=maximize))
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay),
+                         max_grad_norm, world_size, sanitize, grad_scale, seed)
+
+
+class FlatSGD(_FlatOptimizer):
+    """main.py:957 `optim.SGD(lr, momentum=0.9, weight_decay=1e-4)`: dampening
+    0, no Nesterov. One flat momentum buffer (none at momentum=0). As in torch,
+    the buffer starts as the first gradient that is actually stepped: the
+    kernels take `buf = g` while the step count is 1 (the device count under
+    sanitize=True, so a skipped first step leaves the next one to initialise),
+    `buf = momentum*buf + g` afterwards.
+
+    Checkpoints are torch.optim.SGD's: `momentum_buffer` per parameter and no
+    step count. A state_dict with buffers resumes with `buf = momentum*buf + g`
+    (steps_taken() then counts from 1); one without them, or with None entries,
+    resumes with `buf = g`."""
+    _TORCH = torch.optim.SGD
+    _REFUSED = {"nesterov": False, "maximize": False, "dampening": 0}
+
+    def __init__(self, params, lr=7e-4, momentum=0.9, weight_decay=1e-4, max_grad_norm=None,
+                 world_size=1, sanitize=False, grad_scale=1.0, seed=None, dampening=0,
+                 nesterov=False, maximize=False):
+        self._check_refused(dict(dampening=dampening, nesterov=nesterov, maximize=maximize))
+        if momentum < 0:
+            raise ValueError(f"FlatSGD: invalid momentum {momentum}")
+        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay),
+                         max_grad_norm, world_size, sanitize, grad_scale, seed)
+
+    def _alloc_state(self):
+        mu = self.param_groups[0]["momentum"]
+        self.momentum_buffer = torch.zeros_like(self.flat) if mu != 0 else None
+
+    def _moments(self):
+        return [] if self.momentum_buffer is None else [self.momentum_buffer]
+
+    def _hyper_keys(self):
+        return ("lr", "momentum", "weight_decay")
+
+    def _buf(self, grp):
+        if grp["momentum"] != 0 and self.momentum_buffer is None:
+            # torch would start the buffer at this step's gradient; the kernels
+            # decide "first step" from the step count, which has moved on
+            raise ValueError("FlatSGD was built with momentum=0 and holds no momentum buffer; "
+                             "build a new FlatSGD to train with momentum")
+        return self.momentum_buffer if grp["momentum"] != 0 else None
+
+    def _tail_update(self, g, grp, st):
+        call("nsm_sgd_tail", ptr(self.flat), ptr(g), ptr(self._buf(grp)), ptr(self._blk_seg),
+             ptr(self._blk_lo), ptr(self._blk_hi), self._nblk, ptr(self._seg_coef),
+             ptr(self.flags), ptr(self._step_dev), float(grp["lr"]), float(grp["momentum"]),
+             float(grp["weight_decay"]), st)
+
+    def _plain_update(self, g, n, grp, coef, st):
+        call("nsm_sgd_step", ptr(self.flat), ptr(g), ptr(self._buf(grp)), n, float(grp["lr"]),
+             float(grp["momentum"]), float(grp["weight_decay"]), self.step_count, ptr(coef), st)
+
+    def state_dict(self):
+        params = self.param_groups[0]["params"]
+        # torch keeps a buffer once a step was taken with momentum, else no state
+        stepped = self.param_groups[0]["momentum"] != 0 and self.steps_taken() > 0
+        state, off = {}, 0
+        for i, p in enumerate(params):
+            n = p.numel()
+            if stepped:
+                state[i] = {"momentum_buffer": self.momentum_buffer[off:off + n].view_as(p).clone()}
+            off += n
+        grp = self._torch_group_defaults()
+        grp["params"] = list(range(len(params)))
+        return {"state": state, "param_groups": [grp]}
+
+    def load_state_dict(self, sd):
+        params = self.param_groups[0]["params"]
+        grp = self._load_group(sd, ("lr", "momentum", "weight_decay"))
+        bufs = []
+        for i in range(len(params)):
+            st = sd["state"].get(i, sd["state"].get(grp["params"][i]))
+            bufs.append(None if st is None else st.get("momentum_buffer"))
+        have = [b is not None for b in bufs]
+        if any(have) and not all(have):
+            raise ValueError("FlatSGD keeps one first-step state; checkpoint has momentum buffers "
+                             "for some parameters only")
+        mu = self.param_groups[0]["momentum"]
+        if mu != 0 and self.momentum_buffer is None:
+            self.momentum_buffer = torch.zeros_like(self.flat)
+        if all(have) and mu != 0:
+            off = 0
+            with torch.no_grad():
+                for p, b in zip(params, bufs):
+                    n = p.numel()
+                    self.momentum_buffer[off:off + n].copy_(b.reshape(-1))
+                    off += n
+            self._set_steps(1)    # buffers present: the next step is buf = mu*buf + g
+        else:
+            if self.momentum_buffer is not None:
+                self.momentum_buffer.zero_()
+            self._set_steps(0)    # the next step taken initialises buf = g
+
+
+def make_optimizer(params, optimizer_type, lr, **kw):
+    """main.py:952-957 in one call: 'adam' -> Adam(weight_decay=1e-4), 'adamw' ->
+    AdamW(weight_decay=1e-3), anything else -> SGD(momentum=0.9,
+    weight_decay=1e-4), on the flat-buffer optimizers. The comparison is the
+    reference's (exact, case-sensitive); `kw` takes max_grad_norm, world_size,
+    sanitize, grad_scale and seed."""
+    if optimizer_type == 'adam':
+        return FlatAdam(params, lr=lr, weight_decay=1e-4, **kw)
+    elif optimizer_type == 'adamw':
+        return FlatAdamW(params, lr=lr, weight_decay=1e-3, **kw)
+    else:
+        return FlatSGD(params, lr=lr, momentum=0.9, weight_decay=1e-4, **kw)

@@ -4,8 +4,9 @@ The reference's step (main.py:255-423: forward under autocast, the loss,
 `scaler.scale(loss).backward()`, the NaN/Inf census and repair, the
 per-parameter clips, clip_grad_norm_, AdamW) is ~200 kernel launches on this
 path; `GraphedTrainStep` captures forward + loss + backward + the FlatAdamW
-device tail once and replays them as one graph, so the launches no longer pay
-the host's per-launch cost nor the gaps between dispatches.
+(or FlatAdam / FlatSGD) device tail once and replays them as one graph, so the
+launches no longer pay the host's per-launch cost nor the gaps between
+dispatches.
 
 What the graph holds fixed, and how the step stays the reference's:
   * inputs: `step.x` / `step.y` are static buffers — copy each batch into them
@@ -17,13 +18,13 @@ What the graph holds fixed, and how the step stays the reference's:
     reads it, or the step itself every `range_check_every` replays;
   * version counters: each replay bumps those of the parameters and buffers
     (the kernels rewrote them), so infer.GraphedUnet refreshes its layouts;
-  * hyper-parameters passed as kernel arguments (lr, betas, eps, weight decay,
-    max_norm, the loss scale): the step re-captures when one of them changes
-    (an epoch's LambdaLR / max_norm schedule costs one capture);
+  * hyper-parameters passed as kernel arguments (lr, betas or momentum, eps,
+    weight decay, max_norm, the loss scale): the step re-captures when one of
+    them changes (an epoch's LambdaLR / max_norm schedule costs one capture);
   * parameter / buffer addresses: FlatAdamW's flat storage keeps them; a
     re-allocation raises.
 The constructor runs `warmup` eager steps on (x, y) to settle the caches,
-then restores parameters, AdamW moments, the tail's counters and the BN
+then restores parameters, optimizer state, the tail's counters and the BN
 buffers, so building the step changes no training state. Under data
 parallelism (`Unet.data_parallel`) the collectives are captured with the
 rest: the rank-0 BN buffer broadcast at the forward, the two gradient buckets'
@@ -44,11 +45,13 @@ class GraphedTrainStep:
         # are captured too (RCCL kernels recorded into the graph)
         self.dp = model._grad_allreduce is not None
         if not getattr(optimizer, "sanitize", False):
-            # the plain FlatAdamW step passes its step count (AdamW's bias
-            # correction) as a kernel argument, which a graph would freeze; the
-            # reference's tail (sanitize=True) counts on the device
-            raise ValueError("GraphedTrainStep: needs nsm_amd.FlatAdamW(..., sanitize=True), "
-                             "whose device tail keeps the AdamW step count on the device")
+            # the plain step passes its step count (AdamW's / Adam's bias
+            # correction, SGD's first-step buffer initialisation) as a kernel
+            # argument, which a graph would freeze; the reference's tail
+            # (sanitize=True) counts on the device
+            raise ValueError("GraphedTrainStep: needs nsm_amd.FlatAdamW(..., sanitize=True) (or "
+                             "FlatAdam / FlatSGD), whose device tail keeps the optimizer step "
+                             "count on the device")
         self.model, self.loss_fn, self.opt = model, loss_fn, optimizer
         self.loss_scale = float(loss_scale)
         self.x = x.detach().clone().requires_grad_(x.requires_grad)
@@ -63,9 +66,7 @@ class GraphedTrainStep:
         self._capture()
 
     def _hyper(self):
-        g = self.opt.param_groups[0]
-        return (float(g["lr"]), tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"]),
-                self.opt.max_grad_norm, self.opt.grad_scale, self.loss_scale)
+        return self.opt.step_hyper() + (self.loss_scale,)
 
     def _addresses(self):
         return [t.data_ptr() for t in list(self.model.parameters()) + list(self.model.buffers())]
@@ -85,12 +86,11 @@ class GraphedTrainStep:
         return loss.detach()
 
     def _state(self):
-        """Everything a step writes besides its scratch: parameters and AdamW
-        moments (FlatAdamW's flat buffers), the tail's device counters and
-        flags, the BN running statistics and counts."""
-        o = self.opt
-        ts = [o.flat, o.exp_avg, o.exp_avg_sq, o._step_dev, o.flags, o.stat]
-        return ts + [b for b in self.model.buffers()]
+        """Everything a step writes besides its scratch: parameters and the
+        optimizer's state (the flat buffers: AdamW / Adam moments, SGD's
+        momentum buffer), the tail's device counters and flags, the BN running
+        statistics and counts."""
+        return self.opt.step_state() + [b for b in self.model.buffers()]
 
     def _capture(self, warmup=None):
         warmup = self.warmup if warmup is None else warmup
