@@ -770,7 +770,9 @@ int nsm_conv_wgrad_f16(const void* dy, int lddy, const void* x, int ldx, int B, 
                        const float* pro_shift, const float* pro_mask, float slope, float* ws,
                        size_t ws_floats, int cin, int cout, float* dw, void* stream);
 
-/* ---- VGG19 perceptual loss (customLoss.py:7-90, forward only) ------------
+/* ---- VGG19 perceptual loss (customLoss.py:7-90) ---------------------------
+ * The forward (the reference's detached value) and, further down, the
+ * element-wise passes of the opt-in input-gradient chain.
  * nsm_vgg_prep: out[2B*H*W][32] NHWC = (nan_to_num(clamp(v,0,1)) - mean)/denom
  * repeated into channels 0-2 (customLoss.py:44-62), images 0..B-1 from
  * `output`, B..2B-1 from `target` (both [B,1,H,W]); channels 3..31 zero.
@@ -778,6 +780,35 @@ int nsm_conv_wgrad_f16(const void* dy, int lddy, const void* x, int ldx, int B, 
 int nsm_vgg_prep(const float* output, const float* target, int B, int H, int W, float mean,
                  float denom, float* out, void* stream);
 int nsm_maxpool2_fwd(const float* x, int B, int H, int W, int C, float* y, void* stream);
+/* Backward of the stack wrt the OUTPUT images (rows of images 0..B-1 only; the
+ * weights are frozen, the target half gets nothing). fp32 NHWC [rows][C],
+ * C % 4 == 0, contiguous; one writer per element, no atomics (bitwise
+ * reproducible). gscale: device pointer to the upstream gradient (NULL: 1), as
+ * in nsm_l1_loss_bwd. The tap term of a conv output y against the target-half
+ * feature t is coef * gscale * sign(y - t), coef = w_i / N_i (normalised layer
+ * weight over the tap's element count); it is taken on the pre-ReLU tensor and
+ * is therefore not masked.
+ * nsm_vgg_tap_relu_bwd, in place on g [n]:
+ *   g = (relu ? (y > 0 ? g : 0) : g) + (t ? coef * gscale * sign(y - t) : 0);
+ *   overwrite != 0 (t required): nothing arrives from above (the last tap), g
+ *   is not read: g = coef * gscale * sign(y - t).
+ * nsm_maxpool2_bwd: MaxPool2d(2,2) (floor) behind a ReLU, the forward having
+ *   pooled the pre-ReLU y [B*H*W][C]: g_pooled [B*(H/2)*(W/2)][C] goes to each
+ *   window's first maximum in row-major order (strict >, NaN wins: the scan of
+ *   nsm_maxpool2_fwd and of ATen) if that maximum is > 0, all other inputs get
+ *   0 (a trailing odd row / column too); t != NULL adds the tap term of y to
+ *   every element. g_y [B*H*W][C] is written, never read.
+ * nsm_vgg_prep_bwd: adjoint of nsm_vgg_prep from g32 [B*H*W][32], the input
+ *   gradient of features.0: grad[b,0,y,x] (+)= scale * (g32[.][0] + g32[.][1] +
+ *   g32[.][2]) / denom where 0 <= output <= 1 (bounds included, as ATen's
+ *   clamp backward), 0 where output is outside or NaN; accumulate != 0 adds to
+ *   grad (the L1 gradient and this one in one buffer). */
+int nsm_vgg_tap_relu_bwd(float* g, const float* y, const float* t, int64_t n, float coef,
+                         const float* gscale, int relu, int overwrite, void* stream);
+int nsm_maxpool2_bwd(const float* g_pooled, const float* y, const float* t, int B, int H, int W,
+                     int C, float coef, const float* gscale, float* g_y, void* stream);
+int nsm_vgg_prep_bwd(const float* g32, const float* output, int B, int H, int W, float denom,
+                     float scale, float* grad, int accumulate, void* stream);
 
 /* ---- frame loader (setdata.MmapLiverDataset's files) -----
  * nsm_npy_info: shape / dtype (0 f32, 1 f64) / data offset of an .npy file.

@@ -148,6 +148,9 @@ _SIGS = {
     "nsm_conv_fwd_f16": (I, [P, I, I, I, I, I, P, P, I, I, P, I, P, P, P, F, P, P]),
     "nsm_conv_wgrad_f16": (I, [P, I, P, I, I, I, I, I, I, I, P, P, P, F, P, Z, I, I, P, P]),
     "nsm_maxpool2_fwd": (I, [P, I, I, I, I, P, P]),
+    "nsm_vgg_tap_relu_bwd": (I, [P, P, P, L, F, P, I, I, P]),
+    "nsm_maxpool2_bwd": (I, [P, P, P, I, I, I, I, F, P, P, P]),
+    "nsm_vgg_prep_bwd": (I, [P, P, I, I, I, F, F, P, I, P]),
     "nsm_tail_chunk": (L, []),
     "nsm_tail_plan": (I, [P, I, P, P, P, P, I]),
     "nsm_tail_ws_bytes": (Z, [I, I]),

@@ -13,7 +13,12 @@
   loss warns once that its VGG term is 0. Other values: a .pth path, a
   state_dict, a MultiLayerVGGLoss, "random", or False (term off, no warning);
   any `vgg=<callable(out, target)>` overrides. The gradient is the same either
-  way.
+  way. `vgg_grad=True` (opt-in; departs from the reference, matches the paper's
+  loss) keeps the value and lets the VGG term carry its gradient:
+  alpha*sign(o-t)/N + (1-alpha)*dVGG/do, from one autograd node whose backward
+  runs the VGG chain (nsm_amd.vgg) and then accumulates the L1 gradient into
+  the same buffer. It needs nsm_amd's own VGG stack: with `vgg=<callable>` or
+  without weights it raises ValueError.
 * The reference asserts `output.min() >= 0 and output.max() <= 1`
   (customLoss.py:131) with a host sync per call. Here a range-check kernel
   sets a sticky device flag that is copied to pinned host memory
@@ -148,21 +153,59 @@ def l1_loss(output, target, alpha=1.0):
     return _L1Fn.apply(output, target, alpha)
 
 
+class _CustomVggFn(torch.autograd.Function):
+    """CustomLoss(vgg_grad=True): alpha*L1 + (1-alpha)*VGG as ONE node with one
+    gradient tensor: the VGG backward chain writes (1-alpha) * dVGG/do, then
+    nsm_l1_loss_bwd accumulates alpha*sign(o-t)/N into the same buffer."""
+
+    @staticmethod
+    def forward(ctx, o, t, alpha, vgg):
+        from . import ops
+        o_, t_ = vgg._inputs(o, t)
+        n = o_.numel()
+        partial = torch.empty(lib.nsm_loss_blocks(n), dtype=torch.float32, device=o_.device)
+        out = torch.empty((), dtype=torch.float32, device=o_.device)
+        call("nsm_l1_loss_fwd", ptr(o_), ptr(t_), n, float(alpha), ptr(partial), ptr(out), stream())
+        with ops.stage("vgg.fwd"):
+            v, saved = vgg._forward(o_, t_, keep=True)
+        ctx.save_for_backward(o_, t_)
+        ctx.vgg, ctx.acts = vgg, saved
+        ctx.alpha, ctx.oshape = float(alpha), o.shape
+        return out + (1 - alpha) * v     # the arithmetic of the detached default
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import ops
+        o_, t_ = ctx.saved_tensors
+        grad = torch.empty_like(o_)
+        g_ = g.detach().contiguous().to(torch.float32)
+        with ops.stage("vgg.bwd"):
+            ctx.vgg._backward(ctx.acts, o_, g_, grad, scale=1 - ctx.alpha)
+        call("nsm_l1_loss_bwd", ptr(o_), ptr(t_), o_.numel(), ctx.alpha, ptr(g_), ptr(grad), 1,
+             stream())
+        return grad.view(ctx.oshape), None, None, None
+
+
 class L1Loss(nn.Module):
     def forward(self, output, target):
         return l1_loss(output, target)
 
 
 class CustomLoss(nn.Module):
-    def __init__(self, device=None, alpha=0.9, vgg=None, vgg_weights="auto", check_range=True):
+    def __init__(self, device=None, alpha=0.9, vgg=None, vgg_weights="auto", check_range=True,
+                 vgg_grad=False):
         super().__init__()
         self.alpha = alpha
         self.l1 = L1Loss()
+        self.vgg_grad = bool(vgg_grad)
+        if self.vgg_grad and vgg is not None:
+            raise ValueError("CustomLoss(vgg_grad=True) differentiates nsm_amd's own VGG stack: "
+                             "it cannot be combined with a user-supplied vgg=<callable>")
         if vgg is not None and isinstance(vgg_weights, str) and vgg_weights == "auto":
             vgg_weights = None           # an explicit vgg callable wins
         if vgg is None and isinstance(vgg_weights, str) and vgg_weights == "auto":
             vgg_weights = find_vgg19_checkpoint()
-            if vgg_weights is None and not _VGG_WARNED:
+            if vgg_weights is None and not _VGG_WARNED and not self.vgg_grad:
                 _VGG_WARNED.append(True)
                 warnings.warn(
                     "nsm_amd.CustomLoss: no VGG19 ImageNet checkpoint found ($NSM_VGG19_WEIGHTS "
@@ -182,6 +225,10 @@ class CustomLoss(nn.Module):
             else:
                 self.vgg_loss = MultiLayerVGGLoss(device, state_dict=vgg_weights)
             vgg = self.vgg_loss
+        elif self.vgg_grad:
+            raise ValueError("CustomLoss(vgg_grad=True) needs VGG weights (a checkpoint, a "
+                             "state_dict, a MultiLayerVGGLoss or \"random\"): without them the "
+                             "perceptual term is off and has no gradient")
         self.vgg = vgg
         self.device = device
         self.check_range = check_range
@@ -191,6 +238,8 @@ class CustomLoss(nn.Module):
         if self.check_range:
             require_gpu(output, "CustomLoss output")
             self._range.launch(output.detach().contiguous().to(torch.float32))
+        if self.vgg_grad:
+            return _CustomVggFn.apply(output, target, self.alpha, self.vgg_loss)
         loss = l1_loss(output, target, self.alpha)
         if self.vgg is not None:
             v = self.vgg(output, target)
@@ -246,12 +295,14 @@ class PerturbationLoss(nn.Module):
 
 
 class EnhancedCustomLoss(nn.Module):
-    def __init__(self, device=None, alpha=0.9, perturb_weight=0.5, vgg=None, vgg_weights="auto"):
+    def __init__(self, device=None, alpha=0.9, perturb_weight=0.5, vgg=None, vgg_weights="auto",
+                 vgg_grad=False):
         super().__init__()
         self.alpha = alpha
         self.perturb_weight = perturb_weight
         self.l1 = L1Loss()
-        self.base = CustomLoss(device, alpha, vgg=vgg, vgg_weights=vgg_weights)
+        self.vgg_grad = bool(vgg_grad)
+        self.base = CustomLoss(device, alpha, vgg=vgg, vgg_weights=vgg_weights, vgg_grad=vgg_grad)
         self.vgg_loss = getattr(self.base, "vgg_loss", None) or vgg
         self.perturbation_loss = PerturbationLoss()
 
@@ -266,7 +317,12 @@ class EnhancedCustomLoss(nn.Module):
         require_gpu(output, "EnhancedCustomLoss output")
         self.base._range.launch(output.detach().contiguous().to(torch.float32))
         l1 = l1_loss(output, target)
-        if self.vgg_loss is not None:
+        if self.vgg_grad:
+            # the same value, carrying d vgg / d output (autograd adds it to the
+            # L1 node's gradient: the returned losses stay separate tensors)
+            from .vgg import _VggFn
+            vgg = _VggFn.apply(output, target, self.vgg_loss)
+        elif self.vgg_loss is not None:
             vgg = torch.as_tensor(self.vgg_loss(output, target), device=l1.device).detach()
         else:
             vgg = torch.zeros((), device=l1.device)

@@ -1186,6 +1186,49 @@ def maxpool2(x, B, H, W):
     return y
 
 
+def vgg_tap_relu_bwd(g, y, t, coef, gscale, relu=True):
+    """Gradient wrt a VGG conv's pre-ReLU output y [rows, C] (output half), in
+    place on g, the gradient wrt relu(y) (nsm_vgg_tap_relu_bwd):
+    g = (relu ? (y > 0 ? g : 0) : g) + (t is given ? coef * gscale * sign(y - t) : 0).
+    g=None (the last tap: nothing arrives from above): a new tensor holding the
+    tap term alone. gscale: 0-dim device tensor (the upstream gradient) or None."""
+    n = y.numel()
+    over = g is None
+    if over:
+        g = torch.empty_like(y)
+    assert g.numel() == n and g.is_contiguous() and y.is_contiguous()
+    assert t is None or (t.numel() == n and t.is_contiguous())
+    call("nsm_vgg_tap_relu_bwd", ptr(g), ptr(y), ptr(t), n, float(coef), ptr(gscale), int(relu),
+         int(over), stream())
+    return g
+
+
+def maxpool2_bwd(gp, y, t, B, H, W, coef, gscale):
+    """Gradient wrt the pre-ReLU y [B*H*W, C] of maxpool2(relu(y)) from the
+    pooled gradient gp [B*(H/2)*(W/2), C], plus y's tap term when t is given
+    (nsm_maxpool2_bwd)."""
+    C = y.shape[1]
+    assert y.shape[0] == B * H * W and gp.shape == (B * (H // 2) * (W // 2), C)
+    assert y.is_contiguous() and gp.is_contiguous() and (t is None or (
+        t.shape == y.shape and t.is_contiguous()))
+    gy = empty(B * H * W, C, device=y.device)
+    call("nsm_maxpool2_bwd", ptr(gp), ptr(y), ptr(t), B, H, W, C, float(coef), ptr(gscale),
+         ptr(gy), stream())
+    return gy
+
+
+def vgg_prep_bwd(g32, output, denom, grad, scale=1.0, accumulate=False):
+    """Adjoint of vgg_prep for the output images: grad [B,1,H,W] (+)= scale *
+    (g32[:, 0] + g32[:, 1] + g32[:, 2]) / denom where 0 <= output <= 1, else 0
+    (nsm_vgg_prep_bwd); g32 [B*H*W, 32] is the input gradient of features.0."""
+    B, _, H, W = output.shape
+    assert g32.shape == (B * H * W, 32) and g32.is_contiguous()
+    assert grad.numel() == B * H * W and grad.is_contiguous() and output.is_contiguous()
+    call("nsm_vgg_prep_bwd", ptr(g32), ptr(output), B, H, W, float(denom), float(scale),
+         ptr(grad), int(accumulate), stream())
+    return grad
+
+
 def l1_mean(a, b, alpha=1.0):
     """alpha * mean|a - b| over all elements, as a 0-dim device tensor."""
     from ._lib import lib

@@ -18,9 +18,36 @@ conv outputs on the way:
   * per tap: `nsm_l1_loss_fwd` of the output half against the target half,
     scaled by the normalised layer weight.
 
-Forward only (the reference computes it under no_grad and returns a detached
-constant, customLoss.py:66-90). Weights: torchvision's `vgg19().features`
-layout (`features.<idx>.weight/bias`); ImageNet weights are a download the
+By default forward only: the reference computes it under no_grad and returns a
+detached constant (customLoss.py:66-90), so there the term moves a logged
+number and no weight. `differentiable=True` departs from the reference on
+request and matches the paper ("a weighted combination of per-pixel difference
+and VGG-19 perceptual loss"): the same forward (same kernels, same order, the
+same value bitwise) returns a tensor whose backward carries d loss / d output
+down the stack on the device (no host sync, capturable, scaled by the upstream
+gradient read from device memory):
+
+  * per tap, on the pre-ReLU tensor: w_i / N_i * sign(y - t)
+    (`nsm_vgg_tap_relu_bwd`, which also applies the ReLU mask y > 0 to the
+    gradient arriving from above, in place);
+  * MaxPool2d: `nsm_maxpool2_bwd` routes to the first maximum of each window of
+    the pre-ReLU tensor, masked by max > 0, fused with that conv's tap term;
+  * each conv's input gradient on the GEMMs of the U-Net backward: Winograd
+    F(4x4,3x3) with the flipped filters (`wino_weight(flip=True)`) where the
+    forward ran Winograd, the implicit-GEMM conv on the PACK_DGRAD pack for
+    features.0, .2 and .5; half the forward's convolution work (B images, not
+    2B); no weight gradient (frozen weights), nothing for the target half;
+  * `nsm_vgg_prep_bwd`: the three repeated channels summed, / (std + eps),
+    masked by clamp's 0 <= o <= 1.
+
+What the backward reads is kept by the forward: the pre-ReLU output of every
+conv up to the last tap. The batched [2B...] tensors are kept WHOLE (the
+output half is a row prefix of each, the target half is read at the taps; no
+copy pass splits them): 2 x 306 MB per image pair at 512^2, 4.9 GB at B=8,
+alive from the forward to the end of the backward.
+
+Weights: torchvision's `vgg19().features` layout
+(`features.<idx>.weight/bias`); ImageNet weights are a download the
 reference does at construction — offline, pass a local checkpoint
 (`from_torchvision_checkpoint`) or a state_dict. Without one the module is
 randomly initialised (He normal, zero bias): the VALUE is then not the
@@ -59,10 +86,43 @@ def _features():
     return nn.Sequential(*mods)
 
 
+class _VggFn(torch.autograd.Function):
+    """MultiLayerVGGLoss(differentiable=True): the forward's value, and
+    d value / d output from the backward chain (one gradient tensor)."""
+
+    @staticmethod
+    def forward(ctx, output, target, mod):
+        o, t = mod._inputs(output, target)
+        with ops.stage("vgg.fwd"):
+            total, saved = mod._forward(o, t, keep=True)
+        ctx.save_for_backward(o)
+        ctx.mod, ctx.acts, ctx.oshape = mod, saved, output.shape
+        return total
+
+    @staticmethod
+    def backward(ctx, g):
+        o, = ctx.saved_tensors
+        grad = torch.empty_like(o)
+        g_ = g.detach().contiguous().to(torch.float32)
+        with ops.stage("vgg.bwd"):
+            ctx.mod._backward(ctx.acts, o, g_, grad)
+        return grad.view(ctx.oshape), None, None
+
+
 class MultiLayerVGGLoss(nn.Module):
+    """differentiable=False (default): the reference's detached value.
+    differentiable=True: the same value, with its gradient wrt `output` (module
+    docstring). keep_acts=True: every forward leaves `self.last_acts =
+    {conv idx: pre-ReLU output [2B*h*w, C] NHWC}` (rows of the B output images
+    first, then the B target images); otherwise the attribute is None."""
+
     def __init__(self, device=None, feature_layers=(2, 7, 12, 21, 30),
-                 weights=(0.25, 0.25, 0.3, 0.1, 0.1), state_dict=None, seed=0):
+                 weights=(0.25, 0.25, 0.3, 0.1, 0.1), state_dict=None, seed=0,
+                 differentiable=False, keep_acts=False):
         super().__init__()
+        self.differentiable = bool(differentiable)
+        self.keep_acts = bool(keep_acts)
+        self.last_acts = None
         assert len(feature_layers) == len(weights), "feature_layers and weights differ in length"
         self.feature_layers = tuple(int(i) for i in feature_layers)
         for i in self.feature_layers:
@@ -87,7 +147,7 @@ class MultiLayerVGGLoss(nn.Module):
         self.mean = 0.485
         # ATen: (std_tensor + 1e-8) in float32, then a true division
         self.denom = float(np.float32(0.229) + np.float32(1e-8))
-        self._packed = None
+        self._packed = self._bpacked = None
         if device is not None:
             self.to(device)
 
@@ -106,13 +166,42 @@ class MultiLayerVGGLoss(nn.Module):
                 continue
             feats[k] = v
         self.features.load_state_dict(feats)
-        self._packed = None
+        self._packed = self._bpacked = None
+
+    def _key(self):
+        return tuple((m.weight.data_ptr(), m.weight._version) for m in self.features
+                     if isinstance(m, nn.Conv2d))
+
+    def _bplan(self):
+        """{conv idx: input-gradient operands} of the plan's convs, cached under
+        the forward plan's key: ("wino", flipped filters, their max|U| slot,
+        cin_p) where the forward ran Winograd, ("conv", PACK_DGRAD pack, cin_p)
+        elsewhere. Built on the first differentiable call only."""
+        key = self._key()
+        if self._bpacked is not None and self._bpacked[0] == key:
+            return self._bpacked[1]
+        bplan, last = {}, max(self.feature_layers)
+        cin_p = 32
+        for idx, m in enumerate(self.features):
+            if idx > last:
+                break
+            if isinstance(m, nn.Conv2d):
+                cop = ops.pad32(m.out_channels)
+                w = m.weight.detach().float()
+                if cin_p >= WINOGRAD_MIN_CHANNELS:
+                    U = ops.wino_weight(w, cin_p, cop, flip=True, tile=WINO_TILE)
+                    bplan[idx] = ("wino", U, ops.absmax(U) if VGG_F16X2 else None, cin_p)
+                else:
+                    bplan[idx] = ("conv", ops.pack_conv_weight(w, cop, cin_p, ops.PACK_DGRAD),
+                                  cin_p)
+                cin_p = cop
+        self._bpacked = (key, bplan)
+        return bplan
 
     def _plan(self):
         """Packed operands of every conv up to the last tap, cached while the
         weights do not change (frozen in the reference)."""
-        key = tuple((m.weight.data_ptr(), m.weight._version) for m in self.features
-                    if isinstance(m, nn.Conv2d))
+        key = self._key()
         if self._packed is not None and self._packed[0] == key:
             return self._packed[1]
         plan, last = [], max(self.feature_layers)
@@ -138,18 +227,28 @@ class MultiLayerVGGLoss(nn.Module):
         self._packed = (key, plan)
         return plan
 
-    @torch.no_grad()
-    def forward(self, output, target):
+    @staticmethod
+    def _inputs(output, target):
         require_gpu(output, "VGG loss input")
         o = output.detach().to(torch.float32).contiguous()
         t = target.detach().to(device=o.device, dtype=torch.float32).contiguous()
         if o.shape != t.shape or o.dim() != 4 or o.shape[1] != 1:
             raise ValueError(f"VGG loss expects [B,1,H,W] pairs, got {tuple(o.shape)}, {tuple(t.shape)}")
-        with ops.stage("vgg.fwd"):
-            return self._forward(o, t)
+        return o, t
 
-    def _forward(self, o, t):
+    def forward(self, output, target):
+        if self.differentiable:
+            return _VggFn.apply(output, target, self)
+        with torch.no_grad():
+            o, t = self._inputs(output, target)
+            with ops.stage("vgg.fwd"):
+                return self._forward(o, t)
+
+    def _forward(self, o, t, keep=False):
+        """The loss value; keep=True: (value, saved), saved = [(conv idx, its
+        pre-ReLU output [2B*h*w, C], h, w)] for _backward."""
         B, _, H, W = o.shape
+        acts = [] if keep or self.keep_acts else None
         n2 = 2 * B
         cur = ops.vgg_prep(o, t, self.mean, self.denom)
         h, w = H, W
@@ -188,13 +287,62 @@ class MultiLayerVGGLoss(nn.Module):
             else:
                 cur = ops.maxpool2(cur, n2, h, w)
                 h, w = h // 2, w // 2
+            if acts is not None and kind in ("conv", "wino"):
+                acts.append((idx, cur, h, w))
             if idx in self.feature_layers:
                 half = B * h * w
                 i = self.feature_layers.index(idx)
                 terms.append(ops.l1_mean(cur[:half], cur[half:], wts[i]))
         self.last_terms = terms        # weighted per-tap terms (device scalars)
         self.f16x2 = am_v is not None
+        self.last_acts = {a[0]: a[1] for a in acts} if self.keep_acts else None
         total = terms[0]
         for v in terms[1:]:
             total = total + v
-        return total
+        return (total, acts) if keep else total
+
+    def _backward(self, saved, o, gscale, grad, scale=1.0, accumulate=False):
+        """grad [B,1,H,W] (+)= scale * gscale * d value / d o, walking the plan
+        in reverse over `saved` (_forward(keep=True)); gscale: the upstream
+        gradient, a 0-dim device tensor the tap kernels read."""
+        B = o.shape[0]
+        bplan = self._bplan()
+        acts = {a[0]: a[1:] for a in saved}
+        wts = self._wts
+        n_w = sum(1 for b in bplan.values() if b[0] == "wino")
+        am_v = ops.amax_slots(n_w, o.device) if VGG_F16X2 and n_w else None
+        i_w = 0
+        g = None                       # gradient wrt the tensor the step below produced
+        relu = pool = False
+        for step in reversed(self._plan()):
+            idx, kind = step[0], step[1]
+            if kind == "relu":
+                relu = True
+                continue
+            if kind == "pool":
+                pool = True
+                continue
+            y2, h, w = acts[idx]
+            half = B * h * w
+            y, t, coef = y2[:half], None, 0.0
+            if idx in self.feature_layers:
+                t = y2[half:]
+                coef = wts[self.feature_layers.index(idx)] / y.numel()
+            if pool:
+                assert relu and g is not None
+                g = ops.maxpool2_bwd(g, y, t, B, h, w, coef, gscale)
+            elif g is None or relu or t is not None:
+                g = ops.vgg_tap_relu_bwd(g, y, t, coef, gscale, relu=relu)
+            relu = pool = False
+            op = bplan[idx]
+            if op[0] == "wino":
+                _, U, am_u, cin_p = op
+                g = ops.conv3x3_wino(g, B, h, w, U, None, cin_p, tile=WINO_TILE,
+                                     tag=f"vgg.{idx}.dgrad", amax_v=ops.amax_slot(am_v, i_w)
+                                     if am_v is not None else None, amax_u=am_u)
+                i_w += 1
+            else:
+                _, wd, cin_p = op
+                g = ops.conv_fwd(g, B, h, w, wd, None, cin_p, 3, tag=f"vgg.{idx}.dgrad")
+        ops.vgg_prep_bwd(g, o, self.denom, grad, scale=scale, accumulate=accumulate)
+        return grad
