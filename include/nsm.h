@@ -584,6 +584,25 @@ int nsm_expdiff_mean(const float* a, const float* b, int64_t n, float alpha, flo
                      float* out, void* stream);
 int nsm_l1_loss_bwd(const float* o, const float* t, int64_t n, float alpha, const float* gscale,
                     float* grad, int accumulate, void* stream);
+/* The opt-in detail terms of CustomLoss (customLoss.py:139-185) on o, t
+ * [B,1,H,W] fp32, N = B*H*W; filters are cross-correlations zero-padded at each
+ * image's own border:
+ *   HF  = mean|hf(o) - hf(t)|, hf(x) = x - G*x (G: 5x5 Gaussian, sigma 1)
+ *   PEN = sum m|o - t| / (M + 1e-8), m = 0.1 < t < 0.9, M = sum m
+ *   SOB = mean|mag(o) - mag(t)|, mag = sqrt(gx^2 + gy^2 + 1e-6) (3x3 Sobel)
+ * fwd: partial holds 4 * nsm_detail_blocks(B,H,W) floats; out[5] = HF, PEN,
+ *   SOB, M, (base ? *base : 0) + (w_hf*HF + w_pen*PEN) + w_sob*SOB. No atomics.
+ * bwd: grad (+)= d(w_hf*HF + w_pen*PEN + w_sob*SOB)/do * (*gscale), recomputed
+ *   from o and t; mcount: device pointer to M (out + 3 of the forward; may be
+ *   NULL when w_pen == 0); gscale: device scalar (NULL: 1) as in
+ *   nsm_l1_loss_bwd; accumulate != 0 adds into grad. One writer per element. */
+int nsm_detail_blocks(int B, int H, int W);
+int nsm_detail_loss_fwd(const float* o, const float* t, int B, int H, int W, float w_hf,
+                        float w_pen, float w_sob, const float* base, float* partial, float* out,
+                        void* stream);
+int nsm_detail_loss_bwd(const float* o, const float* t, int B, int H, int W, float w_hf,
+                        float w_pen, float w_sob, const float* mcount, const float* gscale,
+                        float* grad, int accumulate, void* stream);
 /* PerturbationLoss.perturb_input (pert_loss.py:26-59):
  * per-channel unbiased std over the batch of NCHW x -> std[C] */
 int nsm_channel_std(const float* x, int B, int C, int H, int W, float* partial, float* std,

@@ -19,6 +19,13 @@
   runs the VGG chain (nsm_amd.vgg) and then accumulates the L1 gradient into
   the same buffer. It needs nsm_amd's own VGG stack: with `vgg=<callable>` or
   without weights it raises ValueError.
+  `detail_weight` / `gradient_weight` (opt-in, default 0: the path above,
+  unchanged) switch on the reference's `enhanced_loss` (customLoss.py:139-185):
+  base + detail_weight*(HF + PEN) + gradient_weight*SOB with the high-frequency
+  L1 (image minus its 5x5 Gaussian blur), the penumbra L1 (0.1 < target < 0.9)
+  and the Sobel-magnitude L1, fused in nsm_detail_loss_fwd/bwd; still one
+  autograd node and one gradient buffer. [B,1,H,W] only (ValueError otherwise).
+  `detail_terms(output, target)` returns the three terms as device scalars.
 * The reference asserts `output.min() >= 0 and output.max() <= 1`
   (customLoss.py:131) with a host sync per call. Here a range-check kernel
   sets a sticky device flag that is copied to pinned host memory
@@ -35,7 +42,9 @@
   CustomLoss uses and otherwise follows the reference: returns
   (total, {'l1_loss', 'vgg_loss', 'perturbation_loss', 'total_loss'}),
   total = alpha*L1 + (1-alpha)*vgg [+ perturb_weight*perturbation while
-  training].
+  training]. `detail_weight` / `gradient_weight` as in CustomLoss: when one
+  is non-zero the detail terms join `total` and the dict gains
+  'high_freq_loss', 'penumbra_loss' and 'gradient_loss' (device scalars).
 * `measure_temporal_instability(frames, motion_vectors=None, alpha=5.0)`:
   pert_loss.py:166-199, mean over consecutive frame pairs of
   mean(exp(alpha*|f_t - f_{t-1}|) - 1) (`nsm_expdiff_mean`).
@@ -186,6 +195,125 @@ class _CustomVggFn(torch.autograd.Function):
         return grad.view(ctx.oshape), None, None, None
 
 
+def _detail_inputs(o, t):
+    """[B,1,H,W] fp32 contiguous output and target, as _L1Fn converts them."""
+    require_gpu(o, "detail-term input")
+    if o.dim() != 4 or o.shape[1] != 1:
+        raise ValueError(f"detail terms: expected a [B,1,H,W] output, got {tuple(o.shape)} (the "
+                         "reference's channel-mean branch, customLoss.py:119, is not supported)")
+    o_ = o.detach().contiguous().to(torch.float32)
+    t_ = t.detach().contiguous().to(device=o.device, dtype=torch.float32)
+    if t_.shape != o_.shape:
+        raise ValueError(f"detail terms: shape mismatch {tuple(o.shape)} vs {tuple(t.shape)}")
+    return o_, t_
+
+
+def _detail_fwd(o_, t_, w_hf, w_pen, w_sob, base=None):
+    """The fused forward: a device vector (HF, PEN, SOB, M, base + weighted sum)."""
+    B, _, H, W = o_.shape
+    nb = lib.nsm_detail_blocks(B, H, W)
+    if nb <= 0:
+        raise ValueError(f"detail terms: unsupported shape {tuple(o_.shape)}")
+    partial = torch.empty(4 * nb, dtype=torch.float32, device=o_.device)
+    vec = torch.empty(5, dtype=torch.float32, device=o_.device)
+    call("nsm_detail_loss_fwd", ptr(o_), ptr(t_), B, H, W, w_hf, w_pen, w_sob, ptr(base),
+         ptr(partial), ptr(vec), stream())
+    return vec
+
+
+def _detail_bwd(o_, t_, w, vec, g_, grad, accumulate):
+    B, _, H, W = o_.shape
+    call("nsm_detail_loss_bwd", ptr(o_), ptr(t_), B, H, W, w[0], w[1], w[2],
+         vec.data_ptr() + 3 * vec.element_size(), ptr(g_), ptr(grad), int(accumulate), stream())
+
+
+class _DetailFn(torch.autograd.Function):
+    """w_hf*HF + w_pen*PEN + w_sob*SOB (customLoss.py:139-185) as one node;
+    also returns the three terms (detached)."""
+
+    @staticmethod
+    def forward(ctx, o, t, w_hf, w_pen, w_sob):
+        o_, t_ = _detail_inputs(o, t)
+        ctx.w = (float(w_hf), float(w_pen), float(w_sob))
+        vec = _detail_fwd(o_, t_, *ctx.w)
+        ctx.save_for_backward(o_, t_, vec)
+        ctx.oshape = o.shape
+        terms = (vec[0], vec[1], vec[2])
+        ctx.mark_non_differentiable(*terms)
+        ctx.set_materialize_grads(False)   # no zero-filled gradients for the three terms
+        return (vec[4],) + terms
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        o_, t_, vec = ctx.saved_tensors
+        grad = torch.empty_like(o_)
+        g_ = g.detach().contiguous().to(torch.float32)
+        _detail_bwd(o_, t_, ctx.w, vec, g_, grad, False)
+        return grad.view(ctx.oshape), None, None, None, None
+
+
+def detail_loss(output, target, hf_weight=0.0, penumbra_weight=0.0, sobel_weight=0.0):
+    """hf_weight*HF + penumbra_weight*PEN + sobel_weight*SOB, differentiable
+    wrt `output` on the fused kernels."""
+    return _DetailFn.apply(output, target, hf_weight, penumbra_weight, sobel_weight)[0]
+
+
+def detail_terms(output, target):
+    """(high_freq_loss, penumbra_loss, gradient_loss) of customLoss.py:139-181
+    as detached device scalars, without a host synchronisation."""
+    o_, t_ = _detail_inputs(output, target)
+    vec = _detail_fwd(o_, t_, 0.0, 0.0, 0.0)
+    return vec[0], vec[1], vec[2]
+
+
+class _CustomDetailFn(torch.autograd.Function):
+    """CustomLoss with a detail weight: base + detail_weight*(HF + PEN) +
+    gradient_weight*SOB as ONE node with one gradient tensor. base is
+    alpha*L1 + (1-alpha)*VGG; the VGG term is `vgg` (nsm_amd's stack, carrying
+    its gradient: vgg_grad=True), or the detached value `vgg_value`, or absent.
+    Backward: the VGG chain (if any), then nsm_l1_loss_bwd, then
+    nsm_detail_loss_bwd accumulate into the same buffer."""
+
+    @staticmethod
+    def forward(ctx, o, t, alpha, vgg, vgg_value, detail_weight, gradient_weight):
+        from . import ops
+        o_, t_ = _detail_inputs(o, t)
+        n = o_.numel()
+        partial = torch.empty(lib.nsm_loss_blocks(n), dtype=torch.float32, device=o_.device)
+        base = torch.empty((), dtype=torch.float32, device=o_.device)
+        call("nsm_l1_loss_fwd", ptr(o_), ptr(t_), n, float(alpha), ptr(partial), ptr(base),
+             stream())
+        ctx.acts = None
+        if vgg is not None:
+            with ops.stage("vgg.fwd"):
+                v, ctx.acts = vgg._forward(o_, t_, keep=True)
+            base = base + (1 - alpha) * v            # the arithmetic of _CustomVggFn
+        elif vgg_value is not None:
+            base = base + (1 - alpha) * vgg_value    # the arithmetic of the detached default
+        ctx.w = (float(detail_weight), float(detail_weight), float(gradient_weight))
+        vec = _detail_fwd(o_, t_, *ctx.w, base=base)
+        ctx.save_for_backward(o_, t_, vec)
+        ctx.vgg, ctx.alpha, ctx.oshape = vgg, float(alpha), o.shape
+        terms = (vec[0], vec[1], vec[2])
+        ctx.mark_non_differentiable(*terms)
+        ctx.set_materialize_grads(False)   # no zero-filled gradients for the three terms
+        return (vec[4],) + terms
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        from . import ops
+        o_, t_, vec = ctx.saved_tensors
+        grad = torch.empty_like(o_)
+        g_ = g.detach().contiguous().to(torch.float32)
+        if ctx.vgg is not None:
+            with ops.stage("vgg.bwd"):
+                ctx.vgg._backward(ctx.acts, o_, g_, grad, scale=1 - ctx.alpha)
+        call("nsm_l1_loss_bwd", ptr(o_), ptr(t_), o_.numel(), ctx.alpha, ptr(g_), ptr(grad),
+             1 if ctx.vgg is not None else 0, stream())
+        _detail_bwd(o_, t_, ctx.w, vec, g_, grad, True)
+        return grad.view(ctx.oshape), None, None, None, None, None, None
+
+
 class L1Loss(nn.Module):
     def forward(self, output, target):
         return l1_loss(output, target)
@@ -193,11 +321,13 @@ class L1Loss(nn.Module):
 
 class CustomLoss(nn.Module):
     def __init__(self, device=None, alpha=0.9, vgg=None, vgg_weights="auto", check_range=True,
-                 vgg_grad=False):
+                 vgg_grad=False, detail_weight=0.0, gradient_weight=0.0):
         super().__init__()
         self.alpha = alpha
         self.l1 = L1Loss()
         self.vgg_grad = bool(vgg_grad)
+        self.detail_weight = float(detail_weight)
+        self.gradient_weight = float(gradient_weight)
         if self.vgg_grad and vgg is not None:
             raise ValueError("CustomLoss(vgg_grad=True) differentiates nsm_amd's own VGG stack: "
                              "it cannot be combined with a user-supplied vgg=<callable>")
@@ -238,6 +368,13 @@ class CustomLoss(nn.Module):
         if self.check_range:
             require_gpu(output, "CustomLoss output")
             self._range.launch(output.detach().contiguous().to(torch.float32))
+        if self.detail_weight != 0.0 or self.gradient_weight != 0.0:
+            v = None
+            if not self.vgg_grad and self.vgg is not None:
+                v = torch.as_tensor(self.vgg(output, target), device=output.device).detach()
+            return _CustomDetailFn.apply(output, target, self.alpha,
+                                         self.vgg_loss if self.vgg_grad else None, v,
+                                         self.detail_weight, self.gradient_weight)[0]
         if self.vgg_grad:
             return _CustomVggFn.apply(output, target, self.alpha, self.vgg_loss)
         loss = l1_loss(output, target, self.alpha)
@@ -296,13 +433,16 @@ class PerturbationLoss(nn.Module):
 
 class EnhancedCustomLoss(nn.Module):
     def __init__(self, device=None, alpha=0.9, perturb_weight=0.5, vgg=None, vgg_weights="auto",
-                 vgg_grad=False):
+                 vgg_grad=False, detail_weight=0.0, gradient_weight=0.0):
         super().__init__()
         self.alpha = alpha
         self.perturb_weight = perturb_weight
         self.l1 = L1Loss()
         self.vgg_grad = bool(vgg_grad)
-        self.base = CustomLoss(device, alpha, vgg=vgg, vgg_weights=vgg_weights, vgg_grad=vgg_grad)
+        self.detail_weight = float(detail_weight)
+        self.gradient_weight = float(gradient_weight)
+        self.base = CustomLoss(device, alpha, vgg=vgg, vgg_weights=vgg_weights, vgg_grad=vgg_grad,
+                               detail_weight=detail_weight, gradient_weight=gradient_weight)
         self.vgg_loss = getattr(self.base, "vgg_loss", None) or vgg
         self.perturbation_loss = PerturbationLoss()
 
@@ -329,6 +469,12 @@ class EnhancedCustomLoss(nn.Module):
         # d(alpha*l1)/do reaches the L1 backward as gscale = alpha: alpha*sign/N
         basic = self.alpha * l1 + (1 - self.alpha) * vgg
         losses = {"l1_loss": l1, "vgg_loss": vgg}
+        if self.detail_weight != 0.0 or self.gradient_weight != 0.0:
+            # customLoss.py:161 + 185, the fused node beside the L1 one
+            d, hf, pen, sob = _DetailFn.apply(output, target, self.detail_weight,
+                                              self.detail_weight, self.gradient_weight)
+            basic = basic + d
+            losses.update(high_freq_loss=hf, penumbra_loss=pen, gradient_loss=sob)
         if self.training and self.perturb_weight > 0:
             pert = self.perturbation_loss(model, inputs, output, noises=noises)
             total = basic + self.perturb_weight * pert
