@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdlib.h>
 #include <string>
 
 #include "../../include/nsm.h"
@@ -288,5 +289,17 @@ __device__ __forceinline__ void h2_store8(bf16_t* row, int c, F8 v, float s) {
 }
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+// ---- environment knobs (host) ------------------------------------------------
+// A knob is read once per process: its reader keeps the value in a function-
+// local static. Unset: dflt; set: atoi(value) != 0 / atoll(value).
+inline bool env_flag(const char* name, bool dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) != 0 : dflt;
+}
+inline long long env_int(const char* name, long long dflt) {
+  const char* e = getenv(name);
+  return e ? atoll(e) : dflt;
+}
 
 }  // namespace nsm

@@ -20,29 +20,19 @@
 // Global -> LDS staging goes through registers (float4 per lane, coalesced
 // along channels), double-buffered: the next slab's global loads are issued
 // before the current slab's MFMAs, and written to the other LDS stage after.
-#include <type_traits>
-
-#include "nsm_common.h"
+//
+// This unit holds the fp32 implicit GEMMs (this kernel, its split forms in
+// nsm_conv_split.inc / nsm_conv_split16.inc, every launch of them) and, from
+// "Winograd F(m x m, 3x3)" on, the Winograd convolutions of every path, whose
+// GEMMs are launches of these kernels or calls into nsm_conv_h2.hip. The h2
+// GEMMs and the 16-bit direct convolutions are units of their own
+// (nsm_conv_h2.hip, nsm_conv_bf16.hip, nsm_conv_f16.hip); what they share with
+// this one is nsm_conv.h.
+#include "nsm_conv.h"
+#include "nsm_conv_split.inc"
+#include "nsm_conv_split16.inc"
 
 namespace nsm {
-
-constexpr int BK = 32;
-constexpr int LDK = BK + 4;
-
-// Branch-free operand loads: buffer_load_dwordx4 through a per-block resource
-// descriptor whose base sits just below the block's lowest address; an
-// invalid lane gets an offset past num_records and the hardware returns 0
-// (zero padding / tails without exec-mask branches).
-constexpr uint32_t OOB = 0x80000000u;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* base, long long floats) {
-  long long bytes = floats * 4;
-  if (bytes > 0x7FFFFFFFll) bytes = 0x7FFFFFFFll;
-  if (bytes < 0) bytes = 0;
-  return __builtin_amdgcn_make_buffer_rsrc((void*)base, (short)0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ f32x4 bload4(__amdgpu_buffer_rsrc_t r, uint32_t byte_off) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0));
-}
 
 // ---------------------------------------------------------------------------
 // Operand loaders. R = rows of the operand tile (BM or BN), NT = threads.
@@ -293,397 +283,6 @@ __device__ __forceinline__ void read_frag(const float* S, int rb, int lane, int 
   }
 }
 
-// ---------------------------------------------------------------------------
-// Epilogues. acc[tm][tn] register i holds C[row][col] with
-//   col = lane & 31, row = (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5).
-// ---------------------------------------------------------------------------
-struct EpiCtx {
-  int m0, n0;  // block origin
-  int mb, nb;  // this wave's tile origin
-  int wm, wn, lane;
-  float* lds;  // the GEMM's LDS array (free after the main loop)
-  int mblk;    // M-block index (BN-partial row)
-  int zslab;   // split-K / batch slab of EpiSlab (blockIdx.z unless remapped)
-};
-
-struct EpiStoreP {
-  float* y;
-  int ldy;
-  const float* bias;
-  float* stats;  // optional BN partials [gridDim.x][2][N]: {sum, M2 about block mean}
-  long long bstride;  // batched GEMM (Winograd): output offset per blockIdx.z
-  // optional eval-mode BN + LeakyReLU (+ skip) on the stored value:
-  // y = lrelu((acc + bias) * act_scale + act_shift, slope) (+ res)
-  const float* act_scale;
-  const float* act_shift;
-  float slope;
-  const float* res;
-  int ldres;
-  int vec;  // 16-B row stores staged through LDS (NSM_F32_EPI_VEC=0: 4-byte stores)
-};
-struct EpiStore {
-  using P = EpiStoreP;
-  template <int TM, int TN, int WM, int WN>
-  __device__ static void apply(const P& e, f32x16 (&acc)[TM][TN], const EpiCtx& cx, int M, int N,
-                               int) {
-    const int col = cx.lane & 31, h = cx.lane >> 5;
-    float* yb = e.y + (size_t)cx.zslab * e.bstride;  // store paths run with zsplit == 1
-    float bv[TN];
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn) {
-      int n = cx.nb + tn * 32 + col;
-      bv[tn] = (e.bias && n < N) ? e.bias[n] : 0.f;
-#pragma unroll
-      for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[tm][tn][i] += bv[tn];
-    }
-    if (e.vec && (e.ldy & 3) == 0 && (((uintptr_t)yb) & 15) == 0 &&
-        (!e.res || ((e.ldres & 3) == 0 && (((uintptr_t)e.res) & 15) == 0))) {
-      // each wave stages its tile as rows in LDS (stride WC + 4 floats: the two
-      // row halves of a store land on different banks) and writes 16-B chunks
-      constexpr int WR = TM * 32, WC = TN * 32, WCP = WC + 4, CPR = WC / 4;
-      float* reg = cx.lds + (cx.wm * WN + cx.wn) * (WR * WCP);
-#pragma unroll
-      for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-        for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-          for (int i = 0; i < 16; ++i)
-            reg[(tm * 32 + (i & 3) + 8 * (i >> 2) + 4 * h) * WCP + tn * 32 + col] = acc[tm][tn][i];
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-      for (int it = 0; it < WR * CPR / 64; ++it) {
-        const int q = it * 64 + cx.lane, r = q / CPR, cc = q - r * CPR;
-        const int m = cx.mb + r, n = cx.nb + cc * 4;
-        if (m >= M || n >= N) continue;
-        f32x4 v = *(const f32x4*)&reg[r * WCP + cc * 4];
-        if (e.act_scale) {
-          const f32x4 a = *(const f32x4*)(e.act_scale + n), b = *(const f32x4*)(e.act_shift + n);
-          v = v * a + b;
-          v = f32x4{lrelu(v.x, e.slope), lrelu(v.y, e.slope), lrelu(v.z, e.slope),
-                    lrelu(v.w, e.slope)};
-          if (e.res) v += *(const f32x4*)(e.res + (size_t)m * e.ldres + n);
-        }
-        *(f32x4*)(yb + (size_t)m * e.ldy + n) = v;
-      }
-      if (!e.stats) return;
-      __syncthreads();  // stats_only reuses the LDS
-      stats_only<TM, TN, WM, WN>(e, acc, cx, M, N);
-      return;
-    }
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn) {
-      int n = cx.nb + tn * 32 + col;
-      if (n >= N) continue;
-      const float asc = e.act_scale ? e.act_scale[n] : 0.f;
-      const float ash = e.act_scale ? e.act_shift[n] : 0.f;
-#pragma unroll
-      for (int tm = 0; tm < TM; ++tm) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          int m = cx.mb + tm * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-          if (m >= M) continue;
-          float v = acc[tm][tn][i];
-          if (e.act_scale) {
-            v = lrelu(v * asc + ash, e.slope);
-            if (e.res) v += e.res[(size_t)m * e.ldres + n];
-          }
-          yb[(size_t)m * e.ldy + n] = v;
-        }
-      }
-    }
-    if (!e.stats) return;
-    stats_only<TM, TN, WM, WN>(e, acc, cx, M, N);
-  }
-  // fused BatchNorm batch statistics of this block's rows (two-pass); also
-  // used by the bf16 store epilogue on its rounded values
-  // RPP: rows per partial; a block of WM*TM*32 rows writes (WM*TM*32)/RPP
-  // partial rows, each over its own group of M-waves
-  template <int TM, int TN, int WM, int WN, int RPP = WM * TM * 32>
-  __device__ static void stats_only(const P& e, f32x16 (&acc)[TM][TN], const EpiCtx& cx, int M,
-                                    int N) {
-    const int col = cx.lane & 31, h = cx.lane >> 5;
-    constexpr int BN = WN * TN * 32;
-    constexpr int G = (WM * TM * 32) / RPP, WG = WM / G;
-    static_assert(G >= 1 && G * RPP == WM * TM * 32 && WG * G == WM, "partial groups");
-    float* red = cx.lds;  // [WM][BN]
-    const int g = cx.wm / WG, w0 = g * WG;
-    const int cnt = min(M - (cx.m0 + g * RPP), RPP);
-    float s[TN];
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn) {
-      float t = 0.f;
-#pragma unroll
-      for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          int m = cx.mb + tm * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-          t += (m < M) ? acc[tm][tn][i] : 0.f;
-        }
-      t += __shfl_xor(t, 32, 64);
-      s[tn] = t;
-    }
-    if (h == 0)
-#pragma unroll
-      for (int tn = 0; tn < TN; ++tn) red[cx.wm * BN + cx.wn * TN * 32 + tn * 32 + col] = s[tn];
-    __syncthreads();
-    float mean[TN], tot[TN];
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn) {
-      float t = 0.f;
-#pragma unroll
-      for (int w = 0; w < WG; ++w) t += red[(w0 + w) * BN + cx.wn * TN * 32 + tn * 32 + col];
-      tot[tn] = t;
-      mean[tn] = t / (float)cnt;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn) {
-      float t = 0.f;
-#pragma unroll
-      for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          int m = cx.mb + tm * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-          float d = acc[tm][tn][i] - mean[tn];
-          t += (m < M) ? d * d : 0.f;
-        }
-      t += __shfl_xor(t, 32, 64);
-      s[tn] = t;
-    }
-    if (h == 0)
-#pragma unroll
-      for (int tn = 0; tn < TN; ++tn) red[cx.wm * BN + cx.wn * TN * 32 + tn * 32 + col] = s[tn];
-    __syncthreads();
-    if (cx.wm == w0 && h == 0 && cnt > 0) {
-      float* pr = e.stats + ((size_t)cx.mblk * G + g) * 2 * N;
-#pragma unroll
-      for (int tn = 0; tn < TN; ++tn) {
-        int n = cx.nb + tn * 32 + col;
-        if (n >= N) continue;
-        float q = 0.f;
-#pragma unroll
-        for (int w = 0; w < WG; ++w) q += red[(w0 + w) * BN + cx.wn * TN * 32 + tn * 32 + col];
-        pr[n] = tot[tn];
-        pr[N + n] = q;
-      }
-    }
-  }
-};
-
-// BN-backward epilogue of the 1x1 input-gradient GEMM of a DoubleConv
-// (g = dA1 = dY2 W2, the gradient wrt the activated output of the block's
-// first BN; Unetmodel.py:22-26). With y = Y1 (that BN's input):
-//   dz = g * lrelu'(y*scale + shift) * mask[b][c]
-// mode 0: partials {sum dz, sum dz*(y-mean)*invstd} per row chunk (the
-//         nsm_bn_bwd_reduce format; chunk = nsm_conv_stat_rows rows), g not stored
-// mode 1: mode 0 and g stored (nsm_bn_bwd_apply then reads it)
-// mode 2: dy = k1*dz + k2*(y-mean) + k3 stored (coef from nsm_bn_bwd_finalize)
-// Modes 0 then 2 run the same GEMM twice, so dA1 never goes through HBM.
-struct BnBwdEpiP {
-  void* out;
-  int ldo;
-  const void* y;
-  int ldy;
-  const float* scale;
-  const float* shift;
-  const float* mean;
-  const float* invstd;
-  const float* coef;
-  const float* mask;  // [B][N] or null
-  FastDiv fdHW;
-  float slope;
-  float* partial;  // [nchunk][2][N]
-  int mode;
-  uint32_t* amax = nullptr;  // mode 2 (fp32): max|dy| written (an h2 scale source)
-  uint32_t* k1dz = nullptr;  // modes 0/1 (fp32): max|scale * dz| (the dy bound's k1 term)
-};
-
-__device__ __forceinline__ f32x4 lrelu_grad_v4(f32x4 z, float slope) {
-  return f32x4{lrelu_grad(z.x, slope), lrelu_grad(z.y, slope), lrelu_grad(z.z, slope),
-               lrelu_grad(z.w, slope)};
-}
-__device__ __forceinline__ f32x4 shfl_xor_v4(f32x4 v, int o) {
-  return f32x4{__shfl_xor(v.x, o, 64), __shfl_xor(v.y, o, 64), __shfl_xor(v.z, o, 64),
-               __shfl_xor(v.w, o, 64)};
-}
-
-// Each wave stages its accumulator tile as rows in LDS (row stride WC + 4
-// floats: the two row halves of a store land on different banks), then every
-// lane keeps ONE 4-column group and walks the rows with 16-B accesses: all Y1
-// loads of the lane issue back to back, the accumulators are dead by then, so
-// the epilogue adds no register pressure to the GEMM loop.
-struct EpiBnBwd {
-  using P = BnBwdEpiP;
-  // Y1 rows of the wave tile, loaded before the GEMM's K loop (gemm_h2_kernel:
-  // with the short K of most 1x1 input gradients the epilogue's Y1 read is the
-  // kernel's main traffic; issued first, it overlaps the operand DMA instead of
-  // following the MFMAs). Lane layout of apply's loop: one 4-column group
-  // (lane % CPR) per lane, rows (it * 64 + lane) / CPR.
-  template <int TM, int TN>
-  struct PreT {
-    static constexpr int NIT = TM * 32 * (TN * 32 / 4) / 64;
-    f32x4 yv[NIT];
-  };
-  template <int TM, int TN, int WM, int WN>
-  __device__ static void prefetch(const P& e, PreT<TM, TN>& pre, int mb, int nb, int lane, int M,
-                                  int N) {
-    constexpr int CPR = TN * 32 / 4;
-    const int n = nb + (lane % CPR) * 4, nc = n < N ? n : 0;
-    const float* __restrict__ Y = (const float*)e.y;
-#pragma unroll
-    for (int it = 0; it < PreT<TM, TN>::NIT; ++it) {
-      const int m = min(mb + (it * 64 + lane) / CPR, M - 1);
-      pre.yv[it] = *(const f32x4*)(Y + (size_t)m * e.ldy + nc);
-    }
-  }
-  // LDS of the h2 GEMMs' epilogue (gemm_h2_kernel): the staged wave tiles, then
-  // the [WM][2][BNT] partial rows
-  template <int TM, int TN, int WM, int WN>
-  static constexpr int lds_bytes() {
-    constexpr int a = WM * WN * TM * 32 * (TN * 32 + 4) * 4, b = WM * 2 * WN * TN * 32 * 4;
-    return a > b ? a : b;
-  }
-  template <int TM, int TN, int WM, int WN>
-  __device__ static void apply(const P& e, f32x16 (&acc)[TM][TN], const EpiCtx& cx, int M, int N,
-                               int) {
-    apply_impl<TM, TN, WM, WN>(e, acc, cx, M, N, nullptr);
-  }
-  template <int TM, int TN, int WM, int WN>
-  __device__ static void apply_pre(const P& e, f32x16 (&acc)[TM][TN], const EpiCtx& cx, int M,
-                                   int N, const PreT<TM, TN>& pre) {
-    apply_impl<TM, TN, WM, WN>(e, acc, cx, M, N, &pre);
-  }
-  template <int TM, int TN, int WM, int WN>
-  __device__ static void apply_impl(const P& e, f32x16 (&acc)[TM][TN], const EpiCtx& cx, int M,
-                                    int N, const PreT<TM, TN>* pre) {
-    const int col = cx.lane & 31, h = cx.lane >> 5;
-    constexpr int BNT = WN * TN * 32, WR = TM * 32, WC = TN * 32, WCP = WC + 4;
-    constexpr int CPR = WC / 4;  // 16-B chunks per row
-    constexpr int NIT = WR * CPR / 64;
-    static_assert(64 % CPR == 0, "a lane keeps one column group");
-    float* reg = cx.lds + (cx.wm * WN + cx.wn) * (WR * WCP);
-    __syncthreads();  // the GEMM's last LDS reads are done everywhere
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-      for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-          reg[(tm * 32 + (i & 3) + 8 * (i >> 2) + 4 * h) * WCP + tn * 32 + col] = acc[tm][tn][i];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const float* __restrict__ Y = (const float*)e.y;
-    float* __restrict__ O = (float*)e.out;
-    const float* __restrict__ mk = e.mask;
-    const bool red = e.mode != 2;
-    const int cc = cx.lane % CPR, n = cx.nb + cc * 4;
-    const bool nok = n < N;
-    const int nc = nok ? n : 0;
-    f32x4 yv[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      if (pre) {
-        yv[it] = pre->yv[it];
-      } else {
-        const int m = min(cx.mb + (it * 64 + cx.lane) / CPR, M - 1);
-        yv[it] = *(const f32x4*)(Y + (size_t)m * e.ldy + nc);
-      }
-    }
-    const f32x4 sc = *(const f32x4*)(e.scale + nc), sh = *(const f32x4*)(e.shift + nc),
-                mu = *(const f32x4*)(e.mean + nc);
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-    const f32x4 is = red ? *(const f32x4*)(e.invstd + nc) : zero;
-    const f32x4 k1 = red ? zero : *(const f32x4*)(e.coef + nc),
-                k2 = red ? zero : *(const f32x4*)(e.coef + N + nc),
-                k3 = red ? zero : *(const f32x4*)(e.coef + 2 * N + nc);
-    f32x4 s1 = zero, s2 = zero;
-    uint32_t am = 0;
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int r = (it * 64 + cx.lane) / CPR, m = cx.mb + r;
-      const bool ok = m < M && nok;
-      const f32x4 g = *(const f32x4*)&reg[r * WCP + cc * 4], v = yv[it];
-      f32x4 dz = g * lrelu_grad_v4(v * sc + sh, e.slope);
-      if (mk) dz = dz * *(const f32x4*)(mk + (size_t)fdiv((uint32_t)min(m, M - 1), e.fdHW) * N + nc);
-      if (!red) {
-        if (ok) {
-          const f32x4 d = k1 * dz + k2 * (v - mu) + k3;
-          *(f32x4*)(O + (size_t)m * e.ldo + n) = d;
-          amax_fold(am, d);
-        }
-      } else if (ok) {
-        s1 += dz;
-        s2 += dz * ((v - mu) * is);
-        if (e.mode == 1) *(f32x4*)(O + (size_t)m * e.ldo + n) = g;
-        if (e.k1dz) amax_fold(am, sc * dz);
-      }
-    }
-    if (!red) {
-      amax_flush(am, e.amax);
-      return;
-    }
-    amax_flush(am, e.k1dz);
-#pragma unroll
-    for (int o = CPR; o < 64; o <<= 1) {
-      s1 += shfl_xor_v4(s1, o);
-      s2 += shfl_xor_v4(s2, o);
-    }
-    // one partial row per block (RPP = BM = nsm_conv_stat_rows): the waves of
-    // one column range meet in LDS, fixed order
-    __syncthreads();
-    float* lds = cx.lds;  // [WM][2][BNT]
-    if (cx.lane < CPR) {
-      *(f32x4*)(lds + (cx.wm * 2) * BNT + cx.wn * WC + cc * 4) = s1;
-      *(f32x4*)(lds + (cx.wm * 2 + 1) * BNT + cx.wn * WC + cc * 4) = s2;
-    }
-    __syncthreads();
-    if (cx.wm == 0) {
-      float* pr = e.partial + (size_t)cx.mblk * 2 * N;
-      for (int j = cx.lane; j < 2 * WC; j += 64) {
-        const int k = j / WC, c = j - k * WC, nn = cx.nb + c;
-        if (nn >= N) continue;
-        float t = 0.f;
-#pragma unroll
-        for (int w = 0; w < WM; ++w) t += lds[(w * 2 + k) * BNT + cx.wn * WC + c];
-        pr[k * N + nn] = t;
-      }
-    }
-  }
-};
-
-struct EpiSlabP {
-  float* ws;
-  int vec;  // EpiSlabV: 16-B row stores staged through LDS
-};
-struct EpiSlab {
-  using P = EpiSlabP;
-  template <int TM, int TN, int WM, int WN>
-  __device__ static void apply(const P& e, f32x16 (&acc)[TM][TN], const EpiCtx& cx, int M, int N,
-                               int split) {
-    const int col = cx.lane & 31, h = cx.lane >> 5;
-    const int mb = cx.mb, nb = cx.nb;
-    float* out = e.ws + (size_t)cx.zslab * M * N;  // slab per (batch, split)
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn) {
-      int n = nb + tn * 32 + col;
-      if (n >= N) continue;
-#pragma unroll
-      for (int tm = 0; tm < TM; ++tm) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          int m = mb + tm * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-          if (m < M) out[(size_t)m * N + n] = acc[tm][tn][i];
-        }
-      }
-    }
-  }
-};
-
 // EpiSlab with the LDS-staged 16-B row stores of EpiStore (fp32 weight-
 // gradient kernels only: their two K-major stages, 64 x (BM + BN + 8) floats,
 // hold the BM x BN tile unpadded — the +4 row pad of EpiStore would not fit at
@@ -834,7 +433,57 @@ __global__ void __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_
   EP::template apply<TM, TN, WM, WN>(ep, acc, cx, M, N, split);
 }
 
-#include "nsm_conv_split.inc"
+// ---- host side ---------------------------------------------------------------
+// fp32 GEMM arithmetic: 0 = fp32 MFMA, 1 = bf16 three-way split, 2 = the
+// f16x2 split where the caller passes the operands' maxima (bf16 split
+// elsewhere). -1: not set yet (env NSM_F32_SPLIT, default 2);
+// nsm_set_f32_split overrides.
+static int g_f32_split = -1;
+static int f32_split_mode() {
+  if (g_f32_split < 0) {
+    const int v = (int)env_int("NSM_F32_SPLIT", 2);
+    g_f32_split = v < 0 ? 0 : (v > 2 ? 2 : v);
+  }
+  return g_f32_split;
+}
+static bool f32_split() { return f32_split_mode() != 0; }
+
+// NSM_F32_XCD2D=1: 2-D fp32 GEMM grids with several N-blocks in the
+// N-fastest XCD order (the N-blocks of one activation panel on one XCD).
+// Measured (B=8 fp32 step, 2 runs each, one box): 636.8 / 638.3 off, 628.4 /
+// 638.6 frames/s on — no gain, off by default.
+static bool f32_xcd2d() { static const bool v = env_flag("NSM_F32_XCD2D", false); return v; }
+
+// the fp32 GEMM launch of every fp32 conv: split kernel or fp32 MFMA kernel.
+// amax (device bits of max|A|, max|B|) selects the f16x2 split
+// (nsm_conv_split16.inc) where the caller has the operands' maxima.
+template <int BM, int BN, int WM, int WN, class AL, class BL, class EP, class AP, class BP>
+static void launch_f32_gemm(dim3 grid, hipStream_t s, const AP& ap, const BP& bp,
+                            const typename EP::P& ep, int M, int N, int K, int kchunk, int zsplit,
+                            AmaxPair amax = AmaxPair{nullptr, nullptr});
+
+template <int BM, int BN, int WM, int WN, class AL, class BL, class EP, class AP, class BP>
+static void launch_f32_gemm(dim3 grid, hipStream_t s, const AP& ap, const BP& bp,
+                            const typename EP::P& ep, int M, int N, int K, int kchunk, int zsplit,
+                            AmaxPair amax) {
+  constexpr int NT = WM * WN * 64;
+  // remap batched / split-K grids (M fastest) and 2-D grids with several
+  // N-blocks (N fastest, NSM_F32_XCD2D) whose block count the 8 XCDs divide
+  const long long total = (long long)grid.x * grid.y * grid.z;
+  const int remap = !split_xcd() || total % 8 != 0 ? 0
+                    : grid.z > 1                   ? 1
+                    : grid.y > 1 && f32_xcd2d()   ? 2
+                                                   : 0;
+  if (amax.on() && f32_split_mode() == 2)
+    hipLaunchKernelGGL((gemm_f32h_kernel<BM, BN, WM, WN, AL, BL, EP, AP, BP>), grid, dim3(NT), 0,
+                       s, ap, bp, ep, M, N, K, kchunk, zsplit, remap, amax);
+  else if (f32_split())
+    hipLaunchKernelGGL((gemm_f32s_kernel<BM, BN, WM, WN, AL, BL, EP, AP, BP>), grid, dim3(NT), 0,
+                       s, ap, bp, ep, M, N, K, kchunk, zsplit, remap);
+  else
+    hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, AL, BL, EP, AP, BP>), grid, dim3(NT), 0, s,
+                       ap, bp, ep, M, N, K, kchunk, zsplit);
+}
 
 // ---------------------------------------------------------------------------
 // Host launchers
@@ -858,31 +507,13 @@ static int launch_conv_fwd(const ConvActP& ap, const RowsKP& bp, const typename 
 // 256-row tiles (4 waves of 64x32: 0.75 fragment reads per MFMA instead of
 // 1) for the 32-channel fp32 convs with >= 2048 of them (conv2 at 256^2):
 // conv2.0 fwd 127 -> 112 us, its dgrad 117 -> 101 us (NSM_N32_BM256=0: 128)
-static bool n32_bm256() {
-  static bool v = [] {
-    const char* e = getenv("NSM_N32_BM256");
-    return !e || atoi(e) != 0;
-  }();
-  return v;
-}
+static bool n32_bm256() { static const bool v = env_flag("NSM_N32_BM256", true); return v; }
 // 256x64 tiles (4 waves of 64x64) for the 64-channel fp32 convs with >= 2048
 // of them (conv2.4, conv8.4 at 256^2 and their input gradients): 118.5 ->
 // 101.9, 78 -> 66-70, 59 -> 55 us per launch (NSM_N64_BM256=0: 128x64)
-static bool n64_bm256() {
-  static bool v = [] {
-    const char* e = getenv("NSM_N64_BM256");
-    return !e || atoi(e) != 0;
-  }();
-  return v;
-}
-static int conv_fwd_bm(long long M, int N) {
-  long long mb128 = ceil_div(M, 128);
-  if (N >= 128) return mb128 * ceil_div(N, 128) >= 512 ? 128 : 64;
-  if (N >= 64) return mb128 * ceil_div(N, 64) >= 512 ? 128 : 64;
-  return mb128 >= 512 ? 128 : 64;
-}
+static bool n64_bm256() { static const bool v = env_flag("NSM_N64_BM256", true); return v; }
 // rows per BN-partial row of the fp32 direct-conv dispatch (dispatch_conv_fwd)
-static int conv_fwd_bm_f(long long M, int N) {
+int conv_fwd_bm_f(long long M, int N) {
   if (N < 64 && n32_bm256() && ceil_div(M, 128) >= 4096) return 256;
   if (N == 64 && n64_bm256() && ceil_div(M, 128) >= 4096) return 256;
   return conv_fwd_bm(M, N);
@@ -947,21 +578,13 @@ static int dispatch_wgrad(int BM, int BN, const PixRowsP& ap, const PixRowsP& bp
   return fail(NSM_E_ARG, "wgrad: no tile %dx%d", BM, BN);
 }
 
-struct WgradPlan {
-  int BM, BN, splits, kchunk;
-  size_t ws_floats;
-};
-
 // NSM_WGRAD_MULTITAP=0: one tap per weight-gradient N tile (register kernels)
 static bool wgrad_multitap_f32() {
-  static bool v = [] {
-    const char* e = getenv("NSM_WGRAD_MULTITAP");
-    return !e || atoi(e) != 0;
-  }();
+  static const bool v = env_flag("NSM_WGRAD_MULTITAP", true);
   return v;
 }
 
-static WgradPlan plan_wgrad(int B, int H, int W, int cin_p, int cout_p, int ksize) {
+WgradPlan plan_wgrad(int B, int H, int W, int cin_p, int cout_p, int ksize) {
   WgradPlan pl;
   const int M = cout_p, N = ksize * ksize * cin_p;
   const long long K = (long long)B * H * W;
@@ -976,10 +599,7 @@ static WgradPlan plan_wgrad(int B, int H, int W, int cin_p, int cout_p, int ksiz
   // and the fp32 partial slabs stay <= 512 MB. (4096 blocks, the round-1
   // policy, made the 1x1 weight gradients of the wide layers write and re-read
   // more partial slabs than operands: conv6.4 128 splits x 2 MB = 268 MB.)
-  static const long long target = [] {
-    const char* e = getenv("NSM_WGRAD_BLOCKS");
-    return e ? atoll(e) : 512ll;
-  }();
+  static const long long target = env_int("NSM_WGRAD_BLOCKS", 512);
   // rounded DOWN: a grid just past the resident slots runs a second round for
   // its last few blocks (conv2.0's 3 N tiles x 171 = 513 blocks took 151.6 us)
   long long want = target / tiles;
@@ -1058,8 +678,8 @@ __global__ void __launch_bounds__(256) splitsum_kernel(const float* __restrict__
 
 // split-K slabs -> dw (reference layout): optional 16-way first stage, then
 // the transposing reduction
-static int wgrad_finish(float* ws, const WgradPlan& pl, int M, int N, int cin_p, int taps, int cin,
-                        int cout, float* dw, hipStream_t s) {
+int wgrad_finish(float* ws, const WgradPlan& pl, int M, int N, int cin_p, int taps, int cin,
+                 int cout, float* dw, hipStream_t s) {
   const float* red_src = ws;
   int red_splits = pl.splits;
   if (pl.splits > 16) {
@@ -1115,15 +735,6 @@ __global__ void pad_vec_kernel(const float* __restrict__ v, int n, int n_p, floa
 // F(4x4): 36 per 16 (4x fewer). Matrices: exact Cook-Toom tables generated by
 // tools/wino_coeffs.py (F(4x4) uses points 0, 1, -1, 1/2, -2 for lower fp32 error).
 // ===========================================================================
-// Bounds of the Winograd transforms, (max_i sum_j |T_ij|)^2 rounded up:
-// which 0 = the input transform B^T d B, 1 = the output-gradient transform
-// A dY A^T, 2 = the filter transform G g G^T. max|transform| <= beta * max|in|
-// (the h2 operands' scale source, nsm_conv_h2.inc)
-__host__ __device__ constexpr float wino_beta(int tile, int which) {
-  return which == 0   ? (tile == 6 ? 225.f : tile == 4 ? 49.f : 4.f)
-         : which == 1 ? (tile == 6 ? 3969.f : tile == 4 ? 225.f : 4.f)
-                      : (tile == 6 ? 1.5625f : tile == 4 ? 3.5f : 2.25f);
-}
 template <int MT> struct WinoMats;
 template <> struct WinoMats<2> {
   static constexpr int A = 4;
@@ -2423,13 +2034,7 @@ static int grid_1d(long long work) {
 using namespace nsm;
 
 // NSM_F32_EPI_VEC=0: the fp32 store epilogue writes 4-byte elements directly
-static int f32_epi_vec() {
-  static int v = [] {
-    const char* e = getenv("NSM_F32_EPI_VEC");
-    return (!e || atoi(e) != 0) ? 1 : 0;
-  }();
-  return v;
-}
+static int f32_epi_vec() { static const int v = env_flag("NSM_F32_EPI_VEC", true); return v; }
 
 
 extern "C" int nsm_pack_conv_weight(const float* w, int cout, int cin, int ksize, int cout_p,
@@ -2470,10 +2075,8 @@ extern "C" int nsm_prep_weights(const NsmPrepJob* jobs_dev, int njobs, long long
   NSM_CHECK_ARG(!max_pass || pmax, "prep_weights: the h2 / f16 jobs need pmax (one word per block)");
   NSM_CHECK_ARG((nzero0 == 0 || zero0) && (nzero1 == 0 || zero1) && nzero0 >= 0 && nzero1 >= 0,
                 "prep_weights: zero ranges");
-  static const bool wide = [] {  // NSM_PREP_WIDE=1: the U jobs by wino_weight_block
-    const char* e = getenv("NSM_PREP_WIDE");
-    return e && atoi(e) != 0;
-  }();
+  // NSM_PREP_WIDE=1: the U jobs by wino_weight_block
+  static const bool wide = env_flag("NSM_PREP_WIDE", false);
   // phase 0 (the slot zeroing and the max|w| pass of the h2 / f16 jobs) where
   // there is something to do: otherwise every block of it would return
   const bool p0 = max_pass || nzero0 > 0 || nzero1 > 0;
@@ -2536,10 +2139,10 @@ extern "C" int nsm_conv_fwd_stats(const float* x, int ldx, int B, int H, int W, 
   return dispatch_conv_fwd<false>(ap, bp, ep, (int)Ml, cout_p, K, s, AmaxPair{amax_x, amax_w});
 }
 
-static int conv_fwd_act_f32(const float* x, int ldx, int B, int H, int W, int cin_p,
-                            const float* wpk, const float* bias, int cout_p, int ksize, float* y,
-                            int ldy, const float* act_scale, const float* act_shift, float slope,
-                            const float* res, int ldres, hipStream_t s) {
+int nsm::conv_fwd_act_f32(const float* x, int ldx, int B, int H, int W, int cin_p,
+                          const float* wpk, const float* bias, int cout_p, int ksize, float* y,
+                          int ldy, const float* act_scale, const float* act_shift, float slope,
+                          const float* res, int ldres, hipStream_t s) {
   NSM_CHECK_ARG(x && wpk && y && act_scale && act_shift, "conv_fwd_act: null pointer");
   NSM_CHECK_ARG(B > 0 && H > 0 && W > 0 && cin_p % 32 == 0 && cout_p % 32 == 0,
                 "conv_fwd_act: bad shape");
@@ -2563,6 +2166,25 @@ static int conv_fwd_act_f32(const float* x, int ldx, int B, int H, int W, int ci
   RowsKP bp{wpk, K, cout_p, 0};
   EpiStoreP ep{y, ldy, bias, nullptr, 0, act_scale, act_shift, slope, res, ldres, f32_epi_vec()};
   return dispatch_conv_fwd<false>(ap, bp, ep, (int)Ml, cout_p, K, s);
+}
+
+int nsm::conv1x1_dgrad_bnbwd_f32(const float* dy2, int lddy2, int B, int H, int W, int cop,
+                                 const float* w2d, int cip, const BnBwdEpiP& ep,
+                                 const uint32_t* amax_dy2, const uint32_t* amax_w, hipStream_t s) {
+  const long long Ml = (long long)B * H * W;
+  ConvActP ap{};
+  ap.x = dy2;
+  ap.ld = lddy2;
+  ap.cin = cop;
+  ap.H = H;
+  ap.W = W;
+  ap.M = (int)Ml;
+  ap.ksize = 1;
+  ap.fdW = make_fastdiv(W);
+  ap.fdH = make_fastdiv(H);
+  RowsKP bp{w2d, cop, cip, 0};
+  return dispatch_conv_fwd<false, EpiBnBwd>(ap, bp, ep, (int)Ml, cip, cop, s,
+                                            AmaxPair{amax_dy2, amax_w});
 }
 
 extern "C" size_t nsm_conv_wgrad_ws(int B, int H, int W, int cin_p, int cout_p, int ksize) {
@@ -2627,22 +2249,6 @@ extern "C" int nsm_conv_wgrad(const float* dy, int lddy, const float* x, int ldx
   return wgrad_finish(ws, pl, M, N, cin_p, ksize * ksize, cin, cout, dw, s);
 }
 
-// ---- Winograd host side: tile in {2, 4} selects F(2x2,3x3) / F(4x4,3x3) -------
-struct WinoGeom {
-  int m, alpha2, TH, TW;
-  long long T;
-};
-
-static bool wino_geom(int tile, int B, int H, int W, WinoGeom& g) {
-  if (tile != 2 && tile != 4 && tile != 6) return false;
-  g.m = tile;
-  g.alpha2 = (tile + 2) * (tile + 2);
-  g.TH = (H + tile - 1) / tile;
-  g.TW = (W + tile - 1) / tile;
-  g.T = (long long)B * g.TH * g.TW;
-  return B > 0 && H > 0 && W > 0 && g.T < (1ll << 30);
-}
-
 extern "C" size_t nsm_wino_ws(int B, int H, int W, int cin_p, int cout_p, int tile) {
   WinoGeom g;
   if (!wino_geom(tile, B, H, W, g)) return 0;
@@ -2704,34 +2310,13 @@ extern "C" int nsm_wino_input(const float* x, int ldx, int B, int H, int W, int 
 // 256x64 tiles for the 64-channel Winograd GEMMs (conv9 at 256^2: fwd 122 ->
 // 109 us, dgrad 116 -> 105 us); NSM_WINO_N64_BM256=0: 128x64
 static bool wino_n64_bm256() {
-  static bool v = [] {
-    const char* e = getenv("NSM_WINO_N64_BM256");
-    return !e || atoi(e) != 0;
-  }();
+  static const bool v = env_flag("NSM_WINO_N64_BM256", true);
   return v;
 }
 
 extern "C" int nsm_wino_gemm(const float* V, const float* U, int B, int H, int W, int cin_p,
                              int cout_p, int tile, float* Mb, void* stream) {
   return nsm_wino_gemm_s(V, U, B, H, W, cin_p, cout_p, tile, Mb, nullptr, nullptr, stream);
-}
-
-extern "C" int nsm_absmax(const float* x, int64_t n, uint32_t* out, void* stream) {
-  NSM_CHECK_ARG(x && out && n > 0, "absmax: bad args");
-  const long long g = std::min<long long>(ceil_div(n, 1024), 2048);
-  hipLaunchKernelGGL(absmax_kernel, dim3((int)g), dim3(256), 0, as_stream(stream), x,
-                     (long long)n, out);
-  NSM_LAUNCH_CHECK("absmax");
-  return 0;
-}
-
-extern "C" int nsm_absmax_bf16(const void* x, int64_t n, uint32_t* out, void* stream) {
-  NSM_CHECK_ARG(x && out && n > 0 && ((uintptr_t)x % 16) == 0, "absmax_bf16: bad args");
-  const long long g = std::min<long long>(ceil_div(n, 2048), 2048);
-  hipLaunchKernelGGL(absmax_bf16_kernel, dim3((int)g), dim3(256), 0, as_stream(stream),
-                     (const bf16_t*)x, (long long)n, out);
-  NSM_LAUNCH_CHECK("absmax_bf16");
-  return 0;
 }
 
 extern "C" int nsm_wino_gemm_s(const float* V, const float* U, int B, int H, int W, int cin_p,
@@ -2771,13 +2356,7 @@ extern "C" int nsm_wino_gemm_s(const float* V, const float* U, int B, int H, int
 // (default): 8-B loads of M — a wave's 64 plane reads carry 512 B each instead
 // of 256 B (tools/ubench/plane_read.hip: the 64-plane read of the transform at
 // 3.84 TB/s with 4-B lanes, 5.69 with 8-B ones); 1: one channel per thread
-static int f6_out_cw() {
-  static int v = [] {
-    const char* e = getenv("NSM_F6_OUT_CW");
-    return (e && atoi(e) == 1) ? 1 : 2;
-  }();
-  return v;
-}
+static int f6_out_cw() { static const int v = env_int("NSM_F6_OUT_CW", 2) == 1 ? 1 : 2; return v; }
 static int wino_out_cw(int tile) { return tile == 6 ? f6_out_cw() : 4; }
 
 static int wino_stat_step(int cout_p, int tile) {
@@ -2816,10 +2395,7 @@ static int wino_stat_resident(int tile) {
 // tile (the plain form's grid), capped at one resident round as below.
 // Interleaved A/B, fp32 B=8 step: conv6 71.8 + 46 (bn_stats) -> 77.9 us
 static bool wino_stat_small() {
-  static bool v = [] {
-    const char* e = getenv("NSM_WINO_STAT_SMALL");
-    return !e || atoi(e) != 0;
-  }();
+  static const bool v = env_flag("NSM_WINO_STAT_SMALL", true);
   return v;
 }
 static long long wino_stat_slots(long long T, int cout_p, int tile) {
@@ -2955,13 +2531,7 @@ __global__ void __launch_bounds__(256) wino_output6_buf_kernel(const float* __re
 }
 
 // NSM_F6_OUT_BUF=0: the generic kernel for the fp32 F(6x6) output transform
-static bool f6_out_buf() {
-  static bool v = [] {
-    const char* e = getenv("NSM_F6_OUT_BUF");
-    return !e || atoi(e) != 0;
-  }();
-  return v;
-}
+static bool f6_out_buf() { static const bool v = env_flag("NSM_F6_OUT_BUF", true); return v; }
 
 static void launch_wino_output6(dim3 grid, hipStream_t s, const float* Mb, int cout_p, int H, int W,
                                 const WinoGeom& g, const float* bias, float* y, int ldy,
@@ -3046,12 +2616,7 @@ extern "C" int nsm_conv3x3_wino(const float* x, int ldx, int B, int H, int W, in
 }
 
 // ---- Winograd weight gradient -------------------------------------------------
-struct WinoWgradPlan {
-  int BM, BN, splits, kchunk;
-  size_t slab_floats, dm_floats;
-};
-
-static WinoWgradPlan plan_wino_wgrad(long long T, int cin_p, int cout_p, int nb) {
+WinoWgradPlan nsm::plan_wino_wgrad(long long T, int cin_p, int cout_p, int nb) {
   WinoWgradPlan p;
   p.BM = cout_p >= 128 ? 128 : (cout_p >= 64 ? 64 : 32);
   p.BN = cin_p >= 128 ? 128 : (cin_p >= 64 ? 64 : 32);
@@ -3140,8 +2705,6 @@ extern "C" int nsm_wino_dual_input_bn(const float* g, int ldg, const float* y, i
 static int wgrad_wino(const float* dy, int lddy, const float* dM_in, const float* V, int B, int H,
                       int W, int cin_p, int cout_p, int cin, int cout, int tile, float* dw,
                       float* ws, size_t ws_floats, void* stream, AmaxPair amax = AmaxPair{});
-static int wgrad_wino_finish(float* slab, const WinoWgradPlan& pl, int nb, int M, int N, int cin,
-                             int cout, int tile, float* dw, hipStream_t s);
 
 extern "C" int nsm_conv3x3_wgrad_wino(const float* dy, int lddy, const float* V, int B, int H,
                                       int W, int cin_p, int cout_p, int cin, int cout, int tile,
@@ -3229,8 +2792,8 @@ static int wgrad_wino(const float* dy, int lddy, const float* dM_in, const float
 
 // split-K partials -> one dU per xi with a parallel, fixed-order sum (the
 // transform kernel then reads alpha^2 values per output weight) -> dw
-static int wgrad_wino_finish(float* slab, const WinoWgradPlan& pl, int nb, int M, int N, int cin,
-                             int cout, int tile, float* dw, hipStream_t s) {
+int nsm::wgrad_wino_finish(float* slab, const WinoWgradPlan& pl, int nb, int M, int N, int cin,
+                           int cout, int tile, float* dw, hipStream_t s) {
   const float* du = slab;
   int du_splits = pl.splits;
   if (pl.splits > 1) {
@@ -3256,35 +2819,6 @@ static int wgrad_wino_finish(float* slab, const WinoWgradPlan& pl, int nb, int M
   return 0;
 }
 
-// The 16-bit conv body twice: bf16 (namespace nsm_bf) and f16 (nsm_h). Not
-// nested in nsm: argument-dependent lookup on nsm's types (F8) would otherwise
-// see nsm's bf16 helpers beside nsm_h's f16 ones.
-namespace nsm_bf {
-using namespace nsm;
-__device__ __forceinline__ f32x16 mfma_s16_32(bf16x8 a, bf16x8 b, f32x16 c, int, int, int) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma_s16_16(bf16x8 a, bf16x8 b, f32x4 c, int, int, int) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-// bits of a value already rounded to bf16 (round_bf)
-__device__ __forceinline__ bf16_t s16_bits(float v) { return (bf16_t)(__float_as_uint(v) >> 16); }
-__device__ __forceinline__ void st8s(bf16_t* p, F8 v) { nsm::st8(p, v); }
-#include "nsm_conv_s16.inc"
-}  // namespace nsm_bf
-namespace nsm_h {
-using namespace nsm;
-#include "nsm_fmt_f16.h"
-#include "nsm_conv_s16.inc"
-}  // namespace nsm_h
-
-using namespace nsm;
-using namespace nsm_bf;
-
-#include "nsm_conv_bf16.inc"
-#include "nsm_conv_h2.inc"
-#include "nsm_conv_h2d.inc"
-
 extern "C" float nsm_wino_beta(int tile, int which) {
   return (tile == 2 || tile == 4 || tile == 6) && which >= 0 && which <= 2 ? wino_beta(tile, which)
                                                                           : 0.f;
@@ -3296,13 +2830,7 @@ extern "C" float nsm_wino_beta(int tile, int which) {
 // 100.6; step 723 -> 716 frames/s — off: the per-thread kernel's source-row
 // reuse already keeps its loads cheap, and the region phase serialises the
 // block's reads before its writes at 3 blocks per CU
-static bool wino_in_lds() {
-  static bool v = [] {
-    const char* e = getenv("NSM_WINO_IN_LDS");
-    return e && atoi(e) != 0;
-  }();
-  return v;
-}
+static bool wino_in_lds() { static const bool v = env_flag("NSM_WINO_IN_LDS", false); return v; }
 
 extern "C" int nsm_wino_input_h2(const float* x, int ldx, int B, int hi, int wi, int H, int W,
                                  int cin_p, int tile, void* Vh, const uint32_t* amax_x,
@@ -3371,13 +2899,7 @@ extern "C" int nsm_wino_dual_input_h2(const float* dy, int lddy, int B, int H, i
 
 // NSM_DUAL_LDS=0: the F(6x6) BN-fused h2 dual transform on the per-thread
 // kernel (wino_dual_kernel) instead of the LDS-region one
-static bool dual_lds() {
-  static bool v = [] {
-    const char* e = getenv("NSM_DUAL_LDS");
-    return !e || atoi(e) != 0;
-  }();
-  return v;
-}
+static bool dual_lds() { static const bool v = env_flag("NSM_DUAL_LDS", true); return v; }
 
 // wino_dual_input_h2 of a BN backward whose apply pass was not run
 // (nsm_wino_dual_input_bn's operands): dY1 = k1 dz + k2 (y - mean) + k3 is
@@ -3416,133 +2938,6 @@ extern "C" int nsm_wino_dual_input_bn_h2(const float* g, int ldg, const float* y
 #undef A_
   NSM_LAUNCH_CHECK("wino_dual_input_bn_h2");
   return 0;
-}
-
-// NSM_H2_WG256=0: the h2 weight gradients keep 128x128 tiles where 256x256 fit
-static bool h2_wg256() {
-  static bool v = [] {
-    const char* e = getenv("NSM_H2_WG256");
-    return !e || atoi(e) != 0;
-  }();
-  return v;
-}
-
-// the h2 weight-gradient plan: plan_wino_wgrad's, or 256x256 tiles (8 waves,
-// the forward's tile) where both channel counts are multiples of 256, with the
-// split count that brings the grid to ~1024 blocks (4 rounds of one block per CU)
-// splits of a batched weight-gradient GEMM over T tiles for ~target blocks
-static void wino_wgrad_resplit(WinoWgradPlan& p, long long T, int cin_p, int cout_p, int nb,
-                               long long target) {
-  const long long tiles = (long long)ceil_div(cout_p, p.BM) * ceil_div(cin_p, p.BN) * nb;
-  long long sp = (target + tiles - 1) / tiles, maxs = (T + 255) / 256;
-  if (sp > maxs) sp = maxs;
-  if (sp > 64) sp = 64;
-  if (sp < 1) sp = 1;
-  long long kc = (T + sp - 1) / sp;
-  kc = (kc + BK - 1) / BK * BK;
-  sp = (T + kc - 1) / kc;
-  p.splits = (int)sp;
-  p.kchunk = (int)kc;
-  p.slab_floats = (size_t)nb * sp * cout_p * cin_p;
-  if (sp > 1) p.slab_floats += (size_t)nb * cout_p * cin_p;
-}
-
-static WinoWgradPlan plan_wino_wgrad_h2(long long T, int cin_p, int cout_p, int nb) {
-  WinoWgradPlan p = plan_wino_wgrad(T, cin_p, cout_p, nb);
-  // the 128 / 64 tiles run two blocks per CU: one round of ~512 blocks
-  // (plan_wino_wgrad's ~4096 wrote 64 x 57 partial dU slabs at conv8; A/B
-  // 4096 / 1024 / 512: 658-659 / 661-663 / 664 frames/s)
-  static const long long target = [] {
-    const char* e = getenv("NSM_H2_WG_BLOCKS");
-    return e ? atoll(e) : 512ll;
-  }();
-  wino_wgrad_resplit(p, T, cin_p, cout_p, nb, target);
-  if (!h2_wg256() || cin_p % 256 || cout_p % 256) return p;
-  p.BM = p.BN = 256;
-  const long long tiles = (long long)(cout_p / 256) * (cin_p / 256) * nb;
-  static const long long target256 = [] {
-    const char* e = getenv("NSM_H2_WG256_BLOCKS");
-    return e ? atoll(e) : 1024ll;
-  }();
-  long long sp = (target256 + tiles - 1) / tiles, maxs = (T + 255) / 256;
-  // a full round of unsplit blocks stays unsplit (conv7: 256 tiles x K = 3872,
-  // no partial slabs, no split sum; A/B 694 -> 698 frames/s against 4 splits)
-  if (tiles >= cu_count()) sp = 1;
-  if (sp > maxs) sp = maxs;
-  if (sp > 64) sp = 64;
-  if (sp < 1) sp = 1;
-  long long kc = (T + sp - 1) / sp;
-  kc = (kc + BK - 1) / BK * BK;
-  sp = (T + kc - 1) / kc;
-  // (conv5's F(4x4) at 32x32: 144 tiles x 2 splits = 288 blocks, measured
-  // 52.5 -> 63.5 us: keep the 128x128 plan under three rounds of blocks)
-  if (tiles * sp < 768 && !(sp == 1 && tiles >= cu_count()))
-    return plan_wino_wgrad(T, cin_p, cout_p, nb);
-  p.splits = (int)sp;
-  p.kchunk = (int)kc;
-  p.slab_floats = (size_t)nb * sp * cout_p * cin_p;
-  if (sp > 1) p.slab_floats += (size_t)nb * cout_p * cin_p;
-  return p;
-}
-
-extern "C" size_t nsm_wino_wgrad_h2_ws(int B, int H, int W, int cin_p, int cout_p, int tile) {
-  WinoGeom g;
-  if (!wino_geom(tile, B, H, W, g)) return 0;
-  return plan_wino_wgrad_h2(g.T, cin_p, cout_p, g.alpha2).slab_floats;
-}
-
-extern "C" int nsm_conv3x3_wgrad_wino_h2(const void* dMh, const void* Vh, int B, int H, int W,
-                                         int cin_p, int cout_p, int cin, int cout, int tile,
-                                         float* dw, float* ws, size_t ws_floats,
-                                         const uint32_t* amax_dy, const uint32_t* amax_x,
-                                         void* stream) {
-  NSM_CHECK_ARG(dMh && Vh && dw && ws && amax_dy && amax_x, "conv3x3_wgrad_wino_h2: null pointer");
-  NSM_CHECK_ARG(cin_p % 32 == 0 && cout_p % 32 == 0 && cin <= cin_p && cout <= cout_p,
-                "conv3x3_wgrad_wino_h2: bad channels");
-  NSM_CHECK_ARG(((uintptr_t)dMh % 16) == 0 && ((uintptr_t)Vh % 16) == 0 && ((uintptr_t)ws % 16) == 0,
-                "conv3x3_wgrad_wino_h2: alignment");
-  WinoGeom g;
-  NSM_CHECK_ARG(wino_geom(tile, B, H, W, g), "conv3x3_wgrad_wino_h2: bad tile or shape");
-  const int nb = g.alpha2;
-  WinoWgradPlan pl = plan_wino_wgrad_h2(g.T, cin_p, cout_p, nb);
-  if (ws_floats < pl.slab_floats) return fail(NSM_E_WS, "conv3x3_wgrad_wino_h2: workspace too small");
-  NSM_CHECK_ARG(g.T * 2 * (long long)std::max(cin_p, cout_p) < (1ll << 30),
-                "conv3x3_wgrad_wino_h2: operand too large");
-  hipStream_t s = as_stream(stream);
-  const int M = cout_p, N = cin_p;
-  const int rc = wino_wgrad_gemm_h2((const bf16_t*)dMh, (const bf16_t*)Vh, g.T, cin_p, cout_p, nb,
-                                    pl.BM, pl.BN, pl.kchunk, pl.splits, ws,
-                                    H2Scale{amax_dy, wino_beta(tile, 1)},
-                                    H2Scale{amax_x, wino_beta(tile, 0)}, s);
-  if (rc) return rc;
-  return wgrad_wino_finish(ws, pl, nb, M, N, cin, cout, tile, dw, s);
-}
-
-extern "C" int nsm_to_h2(const float* x, int64_t rows, int C, const uint32_t* amax, float beta,
-                         void* out, void* stream) {
-  NSM_CHECK_ARG(x && out && amax && rows > 0 && C > 0 && C % 8 == 0 && beta > 0.f,
-                "to_h2: bad args");
-  const long long g = std::min<long long>(ceil_div(rows * (C / 4), 256), 8192);
-  hipLaunchKernelGGL(to_h2_kernel, dim3((int)g), dim3(256), 0, as_stream(stream), x,
-                     (long long)rows, C, H2Scale{amax, beta}, (bf16_t*)out);
-  NSM_LAUNCH_CHECK("to_h2");
-  return 0;
-}
-
-extern "C" int nsm_wino_gemm_h2(const void* V, const void* U, int B, int H, int W, int cin_p,
-                                int cout_p, int tile, float* Mb, const uint32_t* amax_v,
-                                float beta_v, const uint32_t* amax_u, float beta_u,
-                                void* stream) {
-  NSM_CHECK_ARG(V && U && Mb && amax_v && amax_u && cin_p % 32 == 0 && cout_p % 32 == 0,
-                "wino_gemm_h2: bad args");
-  NSM_CHECK_ARG(((uintptr_t)V % 16) == 0 && ((uintptr_t)U % 16) == 0 && ((uintptr_t)Mb % 16) == 0,
-                "wino_gemm_h2: 16B alignment");
-  WinoGeom g;
-  NSM_CHECK_ARG(wino_geom(tile, B, H, W, g), "wino_gemm_h2: bad tile or shape");
-  NSM_CHECK_ARG(g.T * 2 * cin_p < (1ll << 30) && (long long)cout_p * 2 * cin_p < (1ll << 30),
-                "wino_gemm_h2: operand too large");
-  return wino_gemm_h2((const bf16_t*)V, (const bf16_t*)U, g.T, cin_p, cout_p, g.alpha2, Mb,
-                      H2Scale{amax_v, beta_v}, H2Scale{amax_u, beta_u}, as_stream(stream));
 }
 
 // ---- bf16 path: Winograd F(4x4) forward on single-plane scaled f16 operands ----
@@ -3590,13 +2985,7 @@ template <> struct BfLane<2> {
   __device__ static V lrg(V z, float s) { return V{lrelu_grad(z.x, s), lrelu_grad(z.y, s)}; }
 };
 // NSM_F16_TX_CW: 2 (default) or 4 channels per thread in those transforms
-static int f16_tx_cw() {
-  static int v = [] {
-    const char* e = getenv("NSM_F16_TX_CW");
-    return e && atoi(e) == 4 ? 4 : 2;
-  }();
-  return v;
-}
+static int f16_tx_cw() { static const int v = env_int("NSM_F16_TX_CW", 2) == 4 ? 4 : 2; return v; }
 // NSM_F16_OUT_CW: channels per thread of the training step's f16-M output
 // transform alone (4, default: M read as 8-B words; 2: as 4-B ones).
 // Interleaved A/B (bf16 B=64 kernel traces, two rounds): the step's output
@@ -3604,10 +2993,7 @@ static int f16_tx_cw() {
 // 1632.7 frames/s — the 8-B reads outweigh the halved occupancy here, unlike
 // the input and dual transforms (NSM_F16_TX_CW)
 static int f16_out_cw() {
-  static int v = [] {
-    const char* e = getenv("NSM_F16_OUT_CW");
-    return (e && atoi(e) == 2) ? 2 : 4;
-  }();
+  static const int v = env_int("NSM_F16_OUT_CW", 4) == 2 ? 2 : 4;
   return v;
 }
 
@@ -3852,13 +3238,7 @@ __global__ void __launch_bounds__(256) wino_input_f16_up_buf_kernel(
 
 // NSM_F16_UP_BUF=0: the generic kernels for the bf16 x2-upsample input
 // transform and the lazy dual transform (their buffer-offset forms otherwise)
-static bool f16_up_buf() {
-  static bool v = [] {
-    const char* e = getenv("NSM_F16_UP_BUF");
-    return !e || atoi(e) != 0;
-  }();
-  return v;
-}
+static bool f16_up_buf() { static const bool v = env_flag("NSM_F16_UP_BUF", true); return v; }
 
 extern "C" int nsm_wino_input_f16_resize(const void* x, int ldx, int B, int hi, int wi, int H, int W,
                                          int cin_p, int tile, void* V, const uint32_t* amax_x,
@@ -4532,74 +3912,6 @@ extern "C" int nsm_wino_dual_bn_f16(const void* g, int ldg, const void* y, int l
   return 0;
 }
 
-// the weight-gradient plan of the f16 path: the h2 plan's, on its 256 / 128 tiles
-static WinoWgradPlan plan_wino_wgrad_f16(long long T, int cin_p, int cout_p, int nb) {
-  WinoWgradPlan p = plan_wino_wgrad_h2(T, cin_p, cout_p, nb);
-  // NSM_F16_WG_SPLITS: K splits of the 256x256 tiles (A/B)
-  static const long long force = [] {
-    const char* e = getenv("NSM_F16_WG_SPLITS");
-    return e ? atoll(e) : 0ll;
-  }();
-  if (force > 0 && p.BM == 256 && p.BN == 256) {
-    long long sp = force, maxs = (T + 255) / 256;
-    if (sp > maxs) sp = maxs;
-    long long kc = (T + sp - 1) / sp;
-    kc = (kc + BK - 1) / BK * BK;
-    sp = (T + kc - 1) / kc;
-    p.splits = (int)sp;
-    p.kchunk = (int)kc;
-    p.slab_floats = (size_t)nb * sp * cout_p * cin_p;
-    if (sp > 1) p.slab_floats += (size_t)nb * cout_p * cin_p;
-  }
-  if (force <= 0 && p.BM == 256 && p.BN == 256 && f16_wg_kt64()) {
-    // K splits by a round model of the 256x256 blocks (one per CU): rounds x
-    // (K / s x a + b) + the split sum's slab traffic c (s + 1) per tile, a, b,
-    // c fitted on the B=64 step's conv5-conv7 weight gradients (kernel traces,
-    // s = 1..8: conv6 1465 / 1299 / 1296 / 1345 us at s = 1..4, split sum
-    // included; conv5 204 at s = 8 vs 136 at s = 3). The h2 planner's ~4
-    // rounds left conv6 unsplit at 2.25 rounds and conv5 at 512-row splits
-    const long long tiles = (long long)(cout_p / 256) * (cin_p / 256) * nb, cus = cu_count();
-    const double a = 26.4e-3, b = 27.5, c = 0.0524;
-    long long best = 1;
-    double bt = 1e30;
-    for (long long s = 1; s <= 8; ++s) {
-      long long kc = (T + s - 1) / s;
-      kc = (kc + BK - 1) / BK * BK;
-      const long long se = (T + kc - 1) / kc;
-      if (se != s) continue;
-      const double t = (double)((tiles * s + cus - 1) / cus) * ((double)kc * a + b) +
-                       (s > 1 ? c * (double)(s + 1) * (double)tiles : 0.0);
-      if (t < bt) {
-        bt = t;
-        best = s;
-      }
-    }
-    long long kc = (T + best - 1) / best;
-    kc = (kc + BK - 1) / BK * BK;
-    const long long sp = (T + kc - 1) / kc;
-    p.splits = (int)sp;
-    p.kchunk = (int)kc;
-    p.slab_floats = (size_t)nb * sp * cout_p * cin_p;
-    if (sp > 1) p.slab_floats += (size_t)nb * cout_p * cin_p;
-  }
-  if ((p.BM == 256 && p.BN == 256) || (p.BM == 128 && p.BN == 128)) return p;
-  // (the h2 planner's smaller tiles: 128 x 128 with its ~512-block split)
-  p.BM = p.BN = 128;
-  const long long tiles = (long long)ceil_div(cout_p, 128) * ceil_div(cin_p, 128) * nb;
-  long long sp = (512 + tiles - 1) / tiles, maxs = (T + 255) / 256;
-  if (sp > maxs) sp = maxs;
-  if (sp > 64) sp = 64;
-  if (sp < 1) sp = 1;
-  long long kc = (T + sp - 1) / sp;
-  kc = (kc + BK - 1) / BK * BK;
-  sp = (T + kc - 1) / kc;
-  p.splits = (int)sp;
-  p.kchunk = (int)kc;
-  p.slab_floats = (size_t)nb * sp * cout_p * cin_p;
-  if (sp > 1) p.slab_floats += (size_t)nb * cout_p * cin_p;
-  return p;
-}
-
 extern "C" size_t nsm_wino_wgrad_f16_ws(int B, int H, int W, int cin_p, int cout_p, int tile) {
   WinoGeom g;
   if (!wino_geom(tile, B, H, W, g)) return 0;
@@ -4646,88 +3958,3 @@ extern "C" int nsm_set_f32_split(int mode) {
   return prev;
 }
 
-// ---- PMC calibration (tools/pmc_calib.py) -----------------------------------
-// Launches of KNOWN byte counts in the access patterns of this library's
-// kernels, so a rocprofv3 counter (WRITE_SIZE, FETCH_SIZE, TCC_EA0_RDREQ*) can
-// be read against the bytes it should report before it is used on them
-// (MI355X_MICROARCH.md §HBM calibrates only 16-B/lane global loads/stores).
-// kind 0: read-only, global_load_dwordx4 (16 B/lane)
-//      1: read-only, buffer_load ... lds (LDS-DMA, 16 B/lane; the GEMM loaders)
-//      2: write-only, global_store_dwordx4
-//      3: write-only, rows staged in LDS then raw_buffer_store_b128 (the
-//         persistent h2 GEMM's fp32 epilogue)
-//      4: write-only, raw_buffer_store_b64 (its f16-M epilogue)
-//      5: write-only, global_store_dword (4 B/lane)
-//      6: write-only, global_store_dwordx2 (8 B/lane)
-// A read-only kernel writes one dword per block (its checksum) to dst.
-__global__ void __launch_bounds__(256) pmc_calib_kernel(int kind, const u32x4* __restrict__ src,
-                                                        u32x4* __restrict__ dst, long long n16) {
-  __shared__ __attribute__((aligned(16))) bf16_t lds[256 * 8];
-  const long long stride = (long long)gridDim.x * 256;
-  const long long i0 = (long long)blockIdx.x * 256 + threadIdx.x;
-  unsigned acc = 0;
-  if (kind == 0) {
-    for (long long i = i0; i < n16; i += stride) {
-      const u32x4 v = src[i];
-      acc ^= v.x ^ v.y ^ v.z ^ v.w;
-    }
-  } else if (kind == 1) {
-    // every wave DMAs 64 x 16 B per trip into its own LDS slice
-    const __amdgpu_buffer_rsrc_t r =
-        __builtin_amdgcn_make_buffer_rsrc((void*)src, (short)0, 0x7FFFFFFF, 0x00020000);
-    bf16_t* my = lds + (threadIdx.x >> 6) * 512;
-    for (long long b = (long long)blockIdx.x * 256; b < n16; b += stride) {
-      // wave-uniform chunk base; the byte offset of this lane's 16 B (< 2 GB)
-      const long long wb = b + (threadIdx.x & ~63);
-      if (wb < n16) {
-        const uint32_t off = (uint32_t)((wb + (threadIdx.x & 63)) * 16);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void*)my, 16, off, 0, 0, 0);
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const u32x4 v = *(const u32x4*)&lds[threadIdx.x * 8];
-    acc = v.x ^ v.y ^ v.z ^ v.w;
-  } else if (kind == 2) {
-    for (long long i = i0; i < n16; i += stride) dst[i] = u32x4{(unsigned)i, 1u, 2u, 3u};
-  } else if (kind == 3 || kind == 4) {
-    // 16 rows x 64 fp32 per wave staged in LDS (as the epilogue), then the
-    // buffer stores of 16 B (kind 3) or of 8 B f16x4 (kind 4) per lane
-    float* stg = (float*)lds + (threadIdx.x >> 6) * 256;
-    const __amdgpu_buffer_rsrc_t r =
-        __builtin_amdgcn_make_buffer_rsrc((void*)dst, (short)0, 0x7FFFFFFF, 0x00020000);
-    const long long per = kind == 3 ? 1 : 2;  // lanes per 16 B of output
-    const long long nl = n16 * per;           // lane-stores in total
-    for (long long i = i0; i < nl; i += stride) {
-      stg[(threadIdx.x & 63) * 4 + 0] = (float)i;
-      __builtin_amdgcn_wave_barrier();
-      const f32x4 v = *(const f32x4*)&stg[(threadIdx.x & 63) * 4];
-      if (kind == 3)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (uint32_t)(i * 16), 0,
-                                               0);
-      else
-        __builtin_amdgcn_raw_buffer_store_b64(pack_f16x4(v), r, (uint32_t)(i * 8), 0, 0);
-    }
-  } else if (kind == 5) {
-    unsigned* d = (unsigned*)dst;
-    for (long long i = i0; i < n16 * 4; i += stride) d[i] = (unsigned)i;
-  } else if (kind == 6) {
-    u32x2* d = (u32x2*)dst;
-    for (long long i = i0; i < n16 * 2; i += stride) d[i] = u32x2{(unsigned)i, 7u};
-  }
-  if (kind <= 1) {
-    for (int o = 32; o > 0; o >>= 1) acc ^= (unsigned)__shfl_xor((int)acc, o);
-    if ((threadIdx.x & 63) == 0 && acc == 0x9E3779B9u) ((unsigned*)dst)[blockIdx.x] = acc;
-  }
-}
-
-extern "C" int nsm_pmc_calib(int kind, const void* src, void* dst, int64_t bytes, void* stream) {
-  NSM_CHECK_ARG(kind >= 0 && kind <= 6 && bytes > 0 && bytes % 4096 == 0 && bytes < (1ll << 31),
-                "pmc_calib: kind 0..6, bytes a multiple of 4096 below 2 GB");
-  NSM_CHECK_ARG(dst && (kind >= 2 || src), "pmc_calib: null pointer");
-  const long long n16 = bytes / 16;
-  hipLaunchKernelGGL(pmc_calib_kernel, dim3(2048), dim3(256), 0, as_stream(stream), kind,
-                     (const u32x4*)src, (u32x4*)dst, n16);
-  NSM_LAUNCH_CHECK("pmc_calib");
-  return 0;
-}

@@ -1,30 +1,44 @@
-// C entries of the 16-bit-storage implicit-GEMM convolutions (bf16: BASELINE
-// config 3; f16: the fp16-autocast mode). The kernels and entry bodies are in
-// nsm_conv_s16.inc, compiled twice (nsm_bf:: bf16, nsm_h:: f16). Included at
-// the end of nsm_conv.hip; not a separate TU.
+// The bf16 convolutions (BASELINE config 3): the 16-bit implicit-GEMM body
+// nsm_conv_s16.inc instantiated for bf16 (namespace nsm_bf) with its C entries,
+// and the three C entries that dispatch on dtype (nsm_conv_fwd_act,
+// nsm_conv1x1_bnbwd_chunks, nsm_conv1x1_dgrad_bnbwd: their f16 and fp32 cases
+// are calls into nsm_conv_f16.hip / nsm_conv.hip). Includes nsm_conv.h and,
+// inside nsm_bf, nsm_conv_s16.inc.
+#include "nsm_conv.h"
+
+// The 16-bit conv body is compiled twice: here for bf16 (namespace nsm_bf) and
+// in nsm_conv_f16.hip for f16 (nsm_h). Not nested in nsm: argument-dependent
+// lookup on nsm's types (F8) would otherwise see nsm's bf16 helpers beside
+// nsm_h's f16 ones.
+namespace nsm_bf {
+using namespace nsm;
+__device__ __forceinline__ f32x16 mfma_s16_32(bf16x8 a, bf16x8 b, f32x16 c, int, int, int) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x4 mfma_s16_16(bf16x8 a, bf16x8 b, f32x4 c, int, int, int) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+// bits of a value already rounded to bf16 (round_bf)
+__device__ __forceinline__ bf16_t s16_bits(float v) { return (bf16_t)(__float_as_uint(v) >> 16); }
+__device__ __forceinline__ void st8s(bf16_t* p, F8 v) { nsm::st8(p, v); }
+#include "nsm_conv_s16.inc"
+}  // namespace nsm_bf
+
+using namespace nsm;
+using namespace nsm_bf;
 
 extern "C" int nsm_pack_conv_weight_bf16(const float* w, int cout, int cin, int ksize, int cout_p,
                                          int cin_p, int mode, void* out, void* stream) {
-  return nsm_bf::s16_pack_conv_weight(w, cout, cin, ksize, cout_p, cin_p, mode, out, stream);
-}
-extern "C" int nsm_pack_conv_weight_f16(const float* w, int cout, int cin, int ksize, int cout_p,
-                                        int cin_p, int mode, void* out, void* stream) {
-  return nsm_h::s16_pack_conv_weight(w, cout, cin, ksize, cout_p, cin_p, mode, out, stream);
+  return s16_pack_conv_weight(w, cout, cin, ksize, cout_p, cin_p, mode, out, stream);
 }
 
-#define NSM_S16_FWD_ARGS                                                                         \
-  const void *x, int ldx, int B, int H, int W, int cin_p, const void *wpk, const float *bias,   \
-      int cout_p, int ksize, void *y, int ldy, const float *pro_scale, const float *pro_shift, \
-      const float *pro_mask, float slope, float *stats, void *stream
-#define NSM_S16_FWD_PASS                                                                    \
-  x, ldx, B, H, W, cin_p, wpk, bias, cout_p, ksize, y, ldy, pro_scale, pro_shift, pro_mask, \
-      slope, stats, stream
-extern "C" int nsm_conv_fwd_bf16(NSM_S16_FWD_ARGS) { return nsm_bf::s16_conv_fwd(NSM_S16_FWD_PASS); }
-extern "C" int nsm_conv_fwd_f16(NSM_S16_FWD_ARGS) {
-  return nsm_h::s16_conv_fwd(NSM_S16_FWD_PASS);
+extern "C" int nsm_conv_fwd_bf16(const void* x, int ldx, int B, int H, int W, int cin_p,
+                                 const void* wpk, const float* bias, int cout_p, int ksize, void* y,
+                                 int ldy, const float* pro_scale, const float* pro_shift,
+                                 const float* pro_mask, float slope, float* stats, void* stream) {
+  return s16_conv_fwd(x, ldx, B, H, W, cin_p, wpk, bias, cout_p, ksize, y, ldy, pro_scale,
+                      pro_shift, pro_mask, slope, stats, stream);
 }
-#undef NSM_S16_FWD_ARGS
-#undef NSM_S16_FWD_PASS
 
 // BN-partial rows / weight-gradient workspace: the tile plans do not depend on
 // the 16-bit format (the f16 convolutions use these two as well)
@@ -39,21 +53,14 @@ extern "C" size_t nsm_conv_wgrad_bf16_ws(int B, int H, int W, int cin_p, int cou
   return a > b ? a : b;
 }
 
-#define NSM_S16_WG_ARGS                                                                          \
-  const void *dy, int lddy, const void *x, int ldx, int B, int H, int W, int cin_p, int cout_p, \
-      int ksize, const float *pro_scale, const float *pro_shift, const float *pro_mask,         \
-      float slope, float *ws, size_t ws_floats, int cin, int cout, float *dw, void *stream
-#define NSM_S16_WG_PASS                                                                       \
-  dy, lddy, x, ldx, B, H, W, cin_p, cout_p, ksize, pro_scale, pro_shift, pro_mask, slope, ws, \
-      ws_floats, cin, cout, dw, stream
-extern "C" int nsm_conv_wgrad_bf16(NSM_S16_WG_ARGS) {
-  return nsm_bf::s16_conv_wgrad(NSM_S16_WG_PASS);
+extern "C" int nsm_conv_wgrad_bf16(const void* dy, int lddy, const void* x, int ldx, int B, int H,
+                                   int W, int cin_p, int cout_p, int ksize, const float* pro_scale,
+                                   const float* pro_shift, const float* pro_mask, float slope,
+                                   float* ws, size_t ws_floats, int cin, int cout, float* dw,
+                                   void* stream) {
+  return s16_conv_wgrad(dy, lddy, x, ldx, B, H, W, cin_p, cout_p, ksize, pro_scale, pro_shift,
+                        pro_mask, slope, ws, ws_floats, cin, cout, dw, stream);
 }
-extern "C" int nsm_conv_wgrad_f16(NSM_S16_WG_ARGS) {
-  return nsm_h::s16_conv_wgrad(NSM_S16_WG_PASS);
-}
-#undef NSM_S16_WG_ARGS
-#undef NSM_S16_WG_PASS
 
 // ---- eval-mode conv + BN + LeakyReLU (+ skip) in one pass --------------------
 extern "C" int nsm_conv_fwd_act(const void* x, int ldx, int B, int H, int W, int cin_p,
@@ -65,8 +72,8 @@ extern "C" int nsm_conv_fwd_act(const void* x, int ldx, int B, int H, int W, int
     return nsm_bf::s16_conv_fwd_act(x, ldx, B, H, W, cin_p, wpk, bias, cout_p, ksize, y, ldy,
                                  act_scale, act_shift, slope, res, ldres, s);
   if (dtype == NSM_F16)
-    return nsm_h::s16_conv_fwd_act(x, ldx, B, H, W, cin_p, wpk, bias, cout_p, ksize, y, ldy,
-                                       act_scale, act_shift, slope, res, ldres, s);
+    return conv_fwd_act_f16(x, ldx, B, H, W, cin_p, wpk, bias, cout_p, ksize, y, ldy, act_scale,
+                            act_shift, slope, res, ldres, s);
   NSM_CHECK_ARG(dtype == NSM_F32, "conv_fwd_act: dtype %d", dtype);
   return conv_fwd_act_f32((const float*)x, ldx, B, H, W, cin_p, (const float*)wpk, bias, cout_p,
                           ksize, (float*)y, ldy, act_scale, act_shift, slope, (const float*)res,
@@ -115,18 +122,7 @@ extern "C" int nsm_conv1x1_dgrad_bnbwd(const void* dy2, int lddy2, int B, int H,
   if (dtype == NSM_BF16)
     return nsm_bf::s16_conv1x1_dgrad_bnbwd(dy2, lddy2, B, H, W, cop, w2d, cip, ep, s);
   if (dtype == NSM_F16)
-    return nsm_h::s16_conv1x1_dgrad_bnbwd(dy2, lddy2, B, H, W, cop, w2d, cip, ep, s);
-  ConvActP ap{};
-  ap.x = (const float*)dy2;
-  ap.ld = lddy2;
-  ap.cin = cop;
-  ap.H = H;
-  ap.W = W;
-  ap.M = (int)Ml;
-  ap.ksize = 1;
-  ap.fdW = make_fastdiv(W);
-  ap.fdH = make_fastdiv(H);
-  RowsKP bp{(const float*)w2d, cop, cip, 0};
-  return dispatch_conv_fwd<false, EpiBnBwd>(ap, bp, ep, (int)Ml, cip, cop, s,
-                                            AmaxPair{amax_dy2, amax_w});
+    return conv1x1_dgrad_bnbwd_f16(dy2, lddy2, B, H, W, cop, w2d, cip, ep, s);
+  return conv1x1_dgrad_bnbwd_f32((const float*)dy2, lddy2, B, H, W, cop, (const float*)w2d, cip, ep,
+                                 amax_dy2, amax_w, s);
 }

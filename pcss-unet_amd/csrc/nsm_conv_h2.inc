@@ -1,7 +1,6 @@
 // fp32 Winograd GEMMs on PRE-SPLIT f16x2 operands ("h2" tensors), global ->
-// LDS by LDS-DMA. Included in nsm_conv.hip after nsm_conv_bf16.inc (uses the
-// DMA helpers of nsm_conv_bf16_dma.inc and the f16x2 split of
-// nsm_conv_split16.inc).
+// LDS by LDS-DMA. Included at the top of nsm_conv_h2.hip only (uses the LDS-DMA
+// helpers and the f16x2 split helpers of nsm_conv.h).
 //
 // The f16x2 split (nsm_conv_split16.inc) writes each fp32 operand x scaled by
 // s = 2^e as h + l, two fp16 terms. gemm_f32h_kernel does that split in the
@@ -17,7 +16,7 @@
 // h2 layout: a [rows][C] fp32 matrix becomes f16 [rows][2C]; the 8 channels
 // of chunk j are h at 16j .. 16j+7 and l at 16j+8 .. 16j+15. A K-tile of 64
 // f16 columns (32 channels, 2 k-steps of 16) is one 128-B LDS row per M/N row,
-// the MK image of the bf16 DMA kernels (nsm_conv_bf16_dma.inc: 16-B chunks
+// the MK image of the bf16 DMA kernels (nsm_conv_s16_dma.inc: 16-B chunks
 // XOR-swizzled by dswz); the plane-p fragment of k-step s is chunk 4s + 2h + p
 // (h = lane >> 5). KM images (weight gradient: K = Winograd tiles): K-tile of
 // 32 rows x 2R f16 columns, read with ds_read_b64_tr_b16 as the bf16 KM image
@@ -33,7 +32,7 @@
 // fp32 rounding of the sums. Producer and GEMM compute e from the same slot
 // and beta (h2_exp).
 
-// H2Scale, h2_exp, h2_pair_word, h2_pair_off, h2_store4: nsm_conv_split16.inc
+// H2Scale, h2_exp, h2_store4: nsm_common.h; h2_pair_word, h2_pair_off: nsm_conv.h
 
 // epilogues that prefetch operands of their own before the K loop (EP::PreT)
 template <class E, class = void>
@@ -1049,13 +1048,7 @@ static int launch_h2(dim3 grid, hipStream_t s, const typename AL::P& ap, const t
 
 // NSM_H2_MF16=0: the forward / dgrad 256x256 tiles on v_mfma_f32_32x32x16_f16
 // (gemm_h2_kernel) instead of 16x16x32 (gemm_h2q_kernel)
-static bool h2_mf16() {
-  static bool v = [] {
-    const char* e = getenv("NSM_H2_MF16");
-    return !e || atoi(e) != 0;
-  }();
-  return v;
-}
+static bool h2_mf16() { static const bool v = env_flag("NSM_H2_MF16", true); return v; }
 
 template <int BM, int BN, int WM, int WN, class AL, class BL, bool SP = false, bool O16 = false>
 static int launch_h2q(dim3 grid, hipStream_t s, const typename AL::P& ap, const typename BL::P& bp,
@@ -1071,23 +1064,11 @@ static int launch_h2q(dim3 grid, hipStream_t s, const typename AL::P& ap, const 
 
 // NSM_H2P_NFAST=0: the persistent GEMM walks a batch entry's tiles M-fastest
 // instead of N-fastest
-static bool h2p_nfast() {
-  static bool v = [] {
-    const char* e = getenv("NSM_H2P_NFAST");
-    return !e || atoi(e) != 0;
-  }();
-  return v;
-}
+static bool h2p_nfast() { static const bool v = env_flag("NSM_H2P_NFAST", true); return v; }
 
 // NSM_H2_PERSIST=0: one tile per block (gemm_h2q_kernel) instead of the
 // persistent grid (gemm_h2p_kernel)
-static bool h2_persist() {
-  static bool v = [] {
-    const char* e = getenv("NSM_H2_PERSIST");
-    return !e || atoi(e) != 0;
-  }();
-  return v;
-}
+static bool h2_persist() { static const bool v = env_flag("NSM_H2_PERSIST", true); return v; }
 
 template <int BM, int BN, int WM, int WN, class AL, class BL, bool SP = false, bool O16 = false>
 static int launch_h2q_or_p(dim3 grid, hipStream_t s, const typename AL::P& ap,
@@ -1108,21 +1089,16 @@ static int launch_h2q_or_p(dim3 grid, hipStream_t s, const typename AL::P& ap,
 
 // NSM_H2_TILE: force the forward / dgrad tile (0 = policy, 1 = 256x256,
 // 2 = 256x128, 3 = 128x128)
-static int h2_tile_env() {
-  static int v = [] {
-    const char* e = getenv("NSM_H2_TILE");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
+static int h2_tile_env() { static const int v = (int)env_int("NSM_H2_TILE", 0); return v; }
 
 // batched M = T x N = cout GEMMs over K = cin channels of single-plane scaled
 // f16 operands (the bf16 path's Winograd forward: V [nb][T][cin_p], U
 // [nb][cout_p][cin_p]); 256-row tiles, N % 128 == 0 (host-checked)
 // o16: M written as f16 (O16 above) into Mb's first half
-static int wino_gemm_f16(const bf16_t* V, const bf16_t* U, long long T, int cin_p, int cout_p,
-                         int nb, float* Mb, H2Scale sv, H2Scale su, hipStream_t s, bool o16 = false,
-                         int* m16e = nullptr) {
+// (called from nsm_conv_bf16.hip; declared in nsm_conv.h)
+int nsm::wino_gemm_f16(const bf16_t* V, const bf16_t* U, long long T, int cin_p, int cout_p,
+                       int nb, float* Mb, H2Scale sv, H2Scale su, hipStream_t s, bool o16,
+                       int* m16e) {
   const int M = (int)T, N = cout_p, K = cin_p;
   H2RowsP ap{V, cin_p, M, (long long)T * cin_p};
   H2RowsP bp{U, cin_p, N, (long long)cout_p * cin_p};
@@ -1196,13 +1172,7 @@ static int wino_gemm_h2(const bf16_t* V, const bf16_t* U, long long T, int cin_p
 // 723.1 frames/s A/B): each 16x16x32 fragment takes two transposing reads
 // whose addresses depend on the lane through the XOR swizzle, one row-group
 // ahead of its MFMAs, where the 32x32x16 form loads a whole k-step ahead.
-static bool wgrad_q() {
-  static bool v = [] {
-    const char* e = getenv("NSM_WGRAD_Q");
-    return e && atoi(e) != 0;
-  }();
-  return v;
-}
+static bool wgrad_q() { static const bool v = env_flag("NSM_WGRAD_Q", false); return v; }
 
 // split-K launch of gemm_h2q_kernel (the KM weight-gradient form)
 template <int BM, int BN, int WM, int WN, class AL, class BL, bool SP = false>
@@ -1220,21 +1190,16 @@ static int launch_h2qk(dim3 grid, hipStream_t s, const typename AL::P& ap, const
 
 // NSM_F16_WG_KT64=0: the bf16 path's 256x256 Winograd weight-gradient GEMMs on
 // 32-row K-tiles instead of 64-row ones (4 k-steps per barrier)
-static bool f16_wg_kt64() {
-  static bool v = [] {
-    const char* e = getenv("NSM_F16_WG_KT64");
-    return !e || atoi(e) != 0;
-  }();
-  return v;
-}
+static bool f16_wg_kt64() { static const bool v = env_flag("NSM_F16_WG_KT64", true); return v; }
 
 // weight-gradient GEMMs dU[xi][split] = dM[xi]^T V[xi] over the split's
 // Winograd tiles (K): M = cout_p, N = cin_p, KM images of both h2 operands
 // the bf16 path's Winograd weight gradient on single-plane f16 dM / V
 // (F16PixDma, one product per k-step): dU[xi][split] = dM[xi]^T V[xi]
-static int wino_wgrad_gemm_f16(const bf16_t* dM, const bf16_t* V, long long T, int cin_p,
-                               int cout_p, int nb, int BM, int BN, int kchunk, int splits,
-                               float* slab, H2Scale sdm, H2Scale sv, hipStream_t s) {
+// (called from nsm_conv_bf16.hip; declared in nsm_conv.h)
+int nsm::wino_wgrad_gemm_f16(const bf16_t* dM, const bf16_t* V, long long T, int cin_p,
+                             int cout_p, int nb, int BM, int BN, int kchunk, int splits,
+                             float* slab, H2Scale sdm, H2Scale sv, hipStream_t s) {
   const int M = cout_p, N = cin_p, K = (int)T;
   H2PixP ap{dM, cout_p, cout_p, (int)T, T * cout_p};
   H2PixP bp{V, cin_p, cin_p, (int)T, T * cin_p};

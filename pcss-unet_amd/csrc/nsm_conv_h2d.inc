@@ -1,6 +1,6 @@
 // The 1x1 convolutions of the DoubleConv (Unetmodel.py:26) on PRE-SPLIT f16x2
-// operands (h2 tensors, nsm_conv_h2.inc). Included in nsm_conv.hip after
-// nsm_conv_h2.inc.
+// operands (h2 tensors, nsm_conv_h2.inc). Included at the top of
+// nsm_conv_h2.hip only, after nsm_conv_h2.inc.
 //
 // gemm_f32h_kernel (nsm_conv_split16.inc) runs the fp32 1x1 convolutions with
 // the f16x2 split done in its operand loaders: every block that loads an
@@ -78,26 +78,14 @@ struct EpiStoreH {
 // Block tiles of the 1x1 h2 GEMMs (M = pixels, N = output channels of the
 // GEMM). NSM_H2D_TILE forces one: 1 = 256x256, 2 = 256x128, 3 = 128x128,
 // 4 = 256x64, 5 = 128x64, 6 = 128x32 (falling back to the next that divides N).
-static int h2d_tile_env() {
-  static int v = [] {
-    const char* e = getenv("NSM_H2D_TILE");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
+static int h2d_tile_env() { static const int v = (int)env_int("NSM_H2D_TILE", 0); return v; }
 // bnbwd: EpiBnBwd stages the whole wave tile in LDS, which a 256x256 block's
 // 128x64 wave tiles do not fit; with a short K (<= 256 channels) its epilogue
 // (the Y1 read) dominates, so it takes the 128x128 tile that runs two blocks
 // per CU (69.6 KB of LDS) instead of 256x128 at one
 // NSM_H2D_BNB_K: the longest K (f16 columns) for which the BN-backward GEMM
 // takes the two-blocks-per-CU 128x128 tile
-static int h2d_bnb_k() {
-  static int v = [] {
-    const char* e = getenv("NSM_H2D_BNB_K");
-    return e ? atoi(e) : 512;
-  }();
-  return v;
-}
+static int h2d_bnb_k() { static const int v = (int)env_int("NSM_H2D_BNB_K", 512); return v; }
 static int h2d_tile(long long M, int N, int K, bool bnbwd) {
   int t = h2d_tile_env();
   const long long mb = ceil_div(M, 256);
@@ -122,13 +110,7 @@ static int h2d_tile_bm(int t) { return t == 1 || t == 2 || t == 4 ? 256 : 128; }
 // tiles (conv5 / conv6 / conv7: 2-8) the blocks sharing one M tile's A rows run
 // back to back on one XCD, so A comes from HBM once instead of once per N tile
 // (conv6's input gradient: 8 x 67 MB of dY2 re-read)
-static bool h2d_nfast() {
-  static bool v = [] {
-    const char* e = getenv("NSM_H2D_NFAST");
-    return !e || atoi(e) != 0;
-  }();
-  return v;
-}
+static bool h2d_nfast() { static const bool v = env_flag("NSM_H2D_NFAST", true); return v; }
 
 template <int BM, int BN, int WM, int WN, class EP>
 static int launch_h2d(const H2RowsP& ap, const H2RowsP& bp, const typename EP::P& ep, int M, int N,
@@ -168,10 +150,7 @@ static WgradPlan plan_wgrad_h2(long long px, int cin_p, int cout_p) {
   pl.BM = cout_p >= 128 ? 128 : (cout_p >= 64 ? 64 : 32);
   pl.BN = cin_p >= 128 ? 128 : (cin_p >= 64 ? 64 : 32);
   const long long tiles = (long long)ceil_div(cout_p, pl.BM) * ceil_div(cin_p, pl.BN);
-  static const long long target = [] {
-    const char* e = getenv("NSM_H2D_WG_BLOCKS");
-    return e ? atoll(e) : 512ll;
-  }();
+  static const long long target = env_int("NSM_H2D_WG_BLOCKS", 512);
   long long sp = target / tiles;
   const long long maxs = (px + 255) / 256;
   long long slab_cap = (128ll << 20) / ((long long)cout_p * cin_p);
@@ -275,7 +254,7 @@ extern "C" int nsm_conv1x1_wgrad_h2(const void* dyh, const void* xh, int M, int 
 }
 
 // ---- the direct 3x3 convolution (conv2, Cin < 64) on h2 operands ---------------
-// The bf16 LDS-DMA loaders (nsm_conv_bf16_dma.inc) move 16-bit columns: an h2
+// The bf16 LDS-DMA loaders (nsm_conv_s16_loaders.inc) move 16-bit columns: an h2
 // tensor [pixels][2 C] is read by them as a 16-bit tensor of 2 C columns, one
 // K-tile of 64 columns = 32 channels x 2 planes, the MK image FragH2 expects.
 // These adapters give them gemm_h2_kernel's interface (K-tile size, batch

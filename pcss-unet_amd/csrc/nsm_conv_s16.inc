@@ -1,10 +1,11 @@
 // 16-bit-storage MFMA implicit-GEMM convolutions: bf16 (BASELINE config 3)
-// and f16 (the fp16-autocast mode). Included twice from nsm_conv.hip: in
-// namespace nsm (bf16) and in nsm::f16s (f16), where nsm_fmt_f16.h shadows the
+// and f16 (the fp16-autocast mode). This body is compiled twice, once per
+// translation unit: nsm_conv_bf16.hip includes it in namespace nsm_bf (bf16),
+// nsm_conv_f16.hip in namespace nsm_h (f16), where nsm_fmt_f16.h shadows the
 // format helpers this body calls (bf_lo / bf_hi / pack_bf2 / round_bf /
-// s16_bits / ld1 / ld8 / st8 and the mfma_s16_* wrappers). Not a separate TU;
-// the C entries are in nsm_conv_bf16.inc.
-// Included at the end of nsm_conv.hip (shares its helpers); not a separate TU.
+// s16_bits / ld1 / ld8 / st8 and the mfma_s16_* wrappers). Both include
+// nsm_conv.h first (epilogue contexts, bf16 operand images, LDS-DMA helpers,
+// tile plans); the C entries follow the inclusion in each.
 //
 // Storage bf16 (activations, packed weights, activation gradients), products
 // bf16 x bf16 on v_mfma_f32_32x32x16_bf16 with fp32 accumulation; BN
@@ -23,14 +24,8 @@
 // Global loads are 16 B (8 bf16) per lane through the same buffer-descriptor
 // OOB zero-fill as the f32 loaders.
 
-// bf16x8, BKB, LDKB, KMStride, read_frag_b: nsm_conv_split.inc
+// bf16x8, BKB, LDKB, KMStride, read_frag_b, make_rsrc_b: nsm_conv.h
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc_b(const bf16_t* base, long long elems) {
-  long long bytes = elems * 2;
-  if (bytes > 0x7FFFFFFFll) bytes = 0x7FFFFFFFll;
-  if (bytes < 0) bytes = 0;
-  return __builtin_amdgcn_make_buffer_rsrc((void*)base, (short)0, (int)bytes, 0x00020000);
-}
 __device__ __forceinline__ u32x4 bload16(__amdgpu_buffer_rsrc_t r, uint32_t byte_off) {
   return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0));
 }
@@ -54,17 +49,8 @@ __device__ __forceinline__ u32x4 prologue8(u32x4 v, const float* scale, const fl
   return o;
 }
 
-struct ConvActPB {  // im2col of NHWC bf16 activations; K = (tap, channel)
-  const bf16_t* x;
-  int ld, cin, H, W, M, ksize, K;
-  FastDiv fdW, fdH, fdC;
-  const float* scale;
-  const float* shift;
-  const float* mask;
-  int mask_ld, mask_on;
-  float slope;
-  int cm;  // LDS-DMA 3x3: channel-major K-tile order (see ConvActDma::prep)
-};
+// ConvActPB, RowsKPB, PixRowsPB and their LDS-DMA loaders
+#include "nsm_conv_s16_loaders.inc"
 
 template <int R, int NT, bool PRO>
 struct ConvActLoaderB {
@@ -131,12 +117,6 @@ struct ConvActLoaderB {
   }
 };
 
-struct RowsKPB {  // dense bf16 rows [nrows][ldw], K valid columns
-  const bf16_t* w;
-  int ldw, nrows, K;
-  int cin, cm;  // LDS-DMA 3x3: channel-major K-tile order (see ConvActDma::prep)
-};
-
 template <int R, int NT>
 struct RowsKLoaderB {
   static constexpr bool KM = false;
@@ -171,18 +151,6 @@ struct RowsKLoaderB {
     for (int i = 0; i < NPT; ++i) *(u32x4*)&S[(row0 + i * RSTEP) * LDKB + kc] = r[i];
   }
 };
-
-struct PixRowsPB {  // rows = pixels (the wgrad K), columns = bf16 channels
-  const bf16_t* x;
-  int ld, ncols, cin, H, W, M, ksize;
-  FastDiv fdW, fdH;
-  const float* scale;
-  const float* shift;
-  const float* mask;
-  int mask_ld, mask_on;
-  float slope;
-};
-
 
 template <int R, int NT, bool SHIFT, bool PRO>
 struct PixRowsLoaderB {
@@ -646,28 +614,16 @@ __global__ void __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_
 // epilogue (short K for the 64-channel layers); +0.6 % end to end.
 // NSM_BF16_SMALL_STAGES=0 restores the 3/4-stage rings.
 static bool small_stages() {
-  static bool v = [] {
-    const char* e = getenv("NSM_BF16_SMALL_STAGES");
-    return !e || atoi(e) != 0;
-  }();
+  static const bool v = env_flag("NSM_BF16_SMALL_STAGES", true);
   return v;
 }
 
 // NSM_BF16_DMA32=0: the 32-channel 3x3 convs on the register path
-static bool bf16_dma32() {
-  static bool v = [] {
-    const char* e = getenv("NSM_BF16_DMA32");
-    return !e || atoi(e) != 0;
-  }();
-  return v;
-}
+static bool bf16_dma32() { static const bool v = env_flag("NSM_BF16_DMA32", true); return v; }
 
 // NSM_BF16_ONE_STAGE=0: single-K-slab register-path launches keep the 2-stage LDS
 static bool bf16_one_stage() {
-  static bool v = [] {
-    const char* e = getenv("NSM_BF16_ONE_STAGE");
-    return !e || atoi(e) != 0;
-  }();
+  static const bool v = env_flag("NSM_BF16_ONE_STAGE", true);
   return v;
 }
 
@@ -693,29 +649,14 @@ static int launch_conv_fwd_b(const ConvActPB& ap, const RowsKPB& bp, const typen
 }
 
 // NSM_BF16_EPI_VEC=0: the store epilogue writes 2-byte elements directly
-static int bf16_epi_vec() {
-  static int v = [] {
-    const char* e = getenv("NSM_BF16_EPI_VEC");
-    return (!e || atoi(e) != 0) ? 1 : 0;
-  }();
-  return v;
-}
+static int bf16_epi_vec() { static const int v = env_flag("NSM_BF16_EPI_VEC", true); return v; }
 // NSM_BF16_WIDE128=0: the N = 128 DMA convolutions on 256x128 blocks
-static bool bf16_wide128() {
-  static bool v = [] {
-    const char* e = getenv("NSM_BF16_WIDE128");
-    return !e || atoi(e) != 0;
-  }();
-  return v;
-}
+static bool bf16_wide128() { static const bool v = env_flag("NSM_BF16_WIDE128", true); return v; }
 
 // NSM_BF16_DMA_MIN: grid size (in 256x128 blocks) from which the forward
 // takes the 256-row LDS-DMA tiles
 static long long bf16_dma_min_blocks() {
-  static long long v = [] {
-    const char* e = getenv("NSM_BF16_DMA_MIN");
-    return e ? atoll(e) : 480ll;
-  }();
+  static const long long v = env_int("NSM_BF16_DMA_MIN", 480);
   return v;
 }
 // rows per BN-partial row of the bf16 forward tile policy (256-row M-blocks,
@@ -733,13 +674,7 @@ static int conv_fwd_bm_b(long long M, int N) {
 // 512x128 LDS-DMA tiles, whose 128 x 64 wave tiles load Y1 in the epilogue),
 // 1 = 128x128 and 2 = 256x128 DMA tiles with Y1 prefetched before the K loop
 // (EpiBnBwdBP)
-static int bf16_bnb_tile() {
-  static int v = [] {
-    const char* e = getenv("NSM_BF16_BNB_TILE");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
+static int bf16_bnb_tile() { static const int v = (int)env_int("NSM_BF16_BNB_TILE", 0); return v; }
 // the 1x1 shapes the tile knob takes (64-channel K-tiles of the LDS-DMA loader)
 static bool bnb_tiled(int N, int cop) {
   return bf16_bnb_tile() && N % 128 == 0 && cop % DBK == 0 && bf16_dma_mode();
@@ -860,21 +795,12 @@ static int dispatch_wgrad_b(int BM, int BN, const PixRowsPB& ap, const PixRowsPB
 
 // NSM_BF16_WGRAD_MULTITAP=0: one tap per weight-gradient N tile everywhere
 static bool wgrad_multitap() {
-  static bool v = [] {
-    const char* e = getenv("NSM_BF16_WGRAD_MULTITAP");
-    return !e || atoi(e) != 0;
-  }();
+  static const bool v = env_flag("NSM_BF16_WGRAD_MULTITAP", true);
   return v;
 }
 
 // NSM_BF16_WGRAD_WIDE=0 keeps 256x128 weight-gradient tiles where 256x256 fit
-static bool wgrad_wide() {
-  static bool v = [] {
-    const char* e = getenv("NSM_BF16_WGRAD_WIDE");
-    return !e || atoi(e) != 0;
-  }();
-  return v;
-}
+static bool wgrad_wide() { static const bool v = env_flag("NSM_BF16_WGRAD_WIDE", true); return v; }
 
 // Prologue-free weight gradients (every 3x3, and the 1x1 whose activated
 // operand is materialised) run on the LDS-DMA kernel: tile per channel counts
@@ -910,23 +836,7 @@ static bool wgrad_dma_tile(int cin_p, int cout_p, int ksize, bool pro, int& BM, 
 
 // NSM_BF16_WAVEQ=0: split count of the DMA weight gradients without the
 // dispatch-round fit below
-static bool wgrad_waveq() {
-  static bool v = [] {
-    const char* e = getenv("NSM_BF16_WAVEQ");
-    return !e || atoi(e) != 0;
-  }();
-  return v;
-}
-static int cu_count() {
-  static int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-      v = 256;
-    return v;
-  }();
-  return n;
-}
+static bool wgrad_waveq() { static const bool v = env_flag("NSM_BF16_WAVEQ", true); return v; }
 // resident blocks per CU of the DMA weight-gradient tiles (wgrad_dma_tile):
 // LDS ring = STAGES x (BM + BN) x 64 bf16 out of 160 KiB; the 8-wave blocks
 // (~100 VGPRs: 4 waves per SIMD) at most 2, the 4-wave ones at most 8
@@ -1022,7 +932,7 @@ __global__ void pack_weight_bf16_kernel(const float* __restrict__ w, int cout, i
   out[idx] = (bf16_t)(pack_bf2(v, 0.f) & 0xFFFFu);
 }
 
-// ---- the 16-bit entry bodies (C entries: nsm_conv_bf16.inc) -------------------
+// ---- the 16-bit entry bodies (C entries: after the inclusion) -------------------
 static int s16_pack_conv_weight(const float* w, int cout, int cin, int ksize, int cout_p, int cin_p,
                                 int mode, void* out, void* stream) {
   NSM_CHECK_ARG(w && out && cout > 0 && cin > 0 && cout_p >= cout && cin_p >= cin,

@@ -1,6 +1,8 @@
 // LDS-DMA pipelined bf16 implicit-GEMM convolutions (BASELINE config 3).
-// Included from nsm_conv_s16.inc (shares its loaders' parameter blocks and
-// epilogues); not a separate TU.
+// Included from nsm_conv_s16.inc only (shares its loaders' parameter blocks and
+// epilogues), so once per 16-bit format. The format-independent LDS-DMA
+// helpers (dswz, kmswz, dma16, vm_wait, dma_barrier, wait_retire, dma_one,
+// lgkm_fence), which the h2 GEMMs use too, are in nsm_conv.h.
 //
 // For the large prologue-free convolutions: 3x3 forward and input-gradient
 // with Cin % 64 == 0 (conv4..conv8), and the 3x3 weight gradient.
@@ -26,213 +28,6 @@
 //   per 16-lane group, delivered transposed). The 16-B chunk c of pixel row k
 //   sits at c ^ kmswz(k): the 4 rows of a 32-lane group land in distinct 64-B
 //   bank quarters.
-
-constexpr int DBK = 64;
-// 16-B chunk XOR of MK row `row` for BK-wide rows: spreads the rows that share
-// a 256-B bank line ((128 / BK) consecutive rows) over distinct chunks
-template <int BK = DBK>
-__device__ __forceinline__ int dswz(int row) {
-  return (row / (128 / BK)) & (BK / 8 - 1);
-}
-
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, const bf16_t* dst, uint32_t off) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void*)dst, 16, off, 0, 0, 0);
-}
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// every wave's LDS reads done (lgkmcnt) and, with its own DMAs retired by
-// vm_wait before, after this barrier a retired stage is readable and the
-// stage read in the previous iteration is free to refill
-__device__ __forceinline__ void dma_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-template <int LPT, int MAXAHEAD>
-__device__ __forceinline__ void wait_retire(int ahead) {
-  // retire the oldest tile, leave `ahead` (<= MAXAHEAD) younger tiles (LPT DMAs
-  // each) in flight
-  static_assert(MAXAHEAD * LPT <= 63, "vmcnt range");
-  if constexpr (MAXAHEAD >= 1) {
-    if (ahead >= MAXAHEAD) {
-      vm_wait<MAXAHEAD * LPT>();
-      return;
-    }
-    wait_retire<LPT, MAXAHEAD - 1>(ahead);
-  } else {
-    vm_wait<0>();
-  }
-}
-
-// ---- MK loaders (forward / dgrad) --------------------------------------------
-template <int R, int NW, int BK = DBK>
-struct ConvActDma {  // im2col rows of NHWC bf16 activations (one tap per K-tile)
-  static constexpr bool KM = false;
-  static constexpr int CH = BK / 8, RPI = 64 / CH;  // 16-B chunks per row, rows per DMA
-  static constexpr int NI = R / (RPI * NW);         // DMA instructions per wave and K-tile
-  static_assert(NI >= 1 && NI * RPI * NW == R, "dma shape");
-  using P = ConvActPB;
-  __amdgpu_buffer_rsrc_t rsrc;
-  uint32_t base[NI];  // byte offset of (pixel row, swizzled chunk) at tap shift 0
-  int py[NI], px[NI];
-  int tdy, tdx, toff;  // current K-tile: tap offsets and its byte offset
-
-  __device__ void init(const P& p, int m0, int, int, int wid, int lane) {
-    const int base_pix = max(0, m0 - p.W - 1);
-    rsrc = make_rsrc_b(p.x + (size_t)base_pix * p.ld, (long long)(p.M - base_pix) * p.ld);
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const int row = (wid * NI + i) * RPI + lane / CH;
-      int q = m0 + row;
-      const bool v = q < p.M;
-      q = v ? q : 0;
-      const int t = (int)fdiv((uint32_t)q, p.fdW);
-      const int xx = q - t * p.W;
-      const int b = (int)fdiv((uint32_t)t, p.fdH);
-      const int yy = t - b * p.H;
-      base[i] = (uint32_t)((q - base_pix) * p.ld + ((lane % CH) ^ dswz<BK>(row)) * 8) * 2u;
-      px[i] = xx;
-      py[i] = v ? yy : -0x40000000;
-    }
-  }
-  __device__ void prep(const P& p, int k0) {
-    int tap, c0;
-    if (p.cm) {  // K-tile t = (channel chunk j, tap): k0 = (j * 9 + tap) * BK
-      const int t = k0 / BK, j = t / 9;
-      tap = t - j * 9;
-      c0 = j * BK;
-    } else {     // tap-major: k0 = tap * cin + c0
-      tap = (int)fdiv((uint32_t)k0, p.fdC);
-      c0 = k0 - tap * p.cin;
-    }
-    tdy = tdx = 0;
-    if (p.ksize == 3) {
-      tdy = tap / 3 - 1;
-      tdx = tap - (tap / 3) * 3 - 1;
-    }
-    toff = ((tdy * p.W + tdx) * p.ld + c0) * 2;
-  }
-  __device__ void one(const P& p, const bf16_t* stage, int wid, int i) const {
-    const int yy = py[i] + tdy, xx = px[i] + tdx;
-    const bool ok = ((unsigned)yy < (unsigned)p.H) & ((unsigned)xx < (unsigned)p.W);
-    // (a halo row's offset may wrap negative: it carries the OOB bit anyway)
-    dma16(rsrc, stage + (wid * NI + i) * 512, (base[i] + (uint32_t)toff) | (ok ? 0u : OOB));
-  }
-};
-
-template <int R, int NW, int BK = DBK>
-struct RowsKDma {  // dense bf16 rows [nrows][ldw] (packed weights)
-  static constexpr bool KM = false;
-  static constexpr int CH = BK / 8, RPI = 64 / CH;
-  static constexpr int NI = R / (RPI * NW);
-  static_assert(NI >= 1 && NI * RPI * NW == R, "dma shape");
-  using P = RowsKPB;
-  __amdgpu_buffer_rsrc_t rsrc;
-  uint32_t base[NI];
-  uint32_t koff;
-
-  __device__ void init(const P& p, int n0, int, int, int wid, int lane) {
-    rsrc = make_rsrc_b(p.w + (size_t)n0 * p.ldw, (long long)(p.nrows - n0) * p.ldw);
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const int row = (wid * NI + i) * RPI + lane / CH;
-      base[i] = ((uint32_t)(row * p.ldw + ((lane % CH) ^ dswz<BK>(row)) * 8) * 2u) |
-                (n0 + row < p.nrows ? 0u : OOB);
-    }
-  }
-  __device__ void prep(const P& p, int k0) {
-    int k = k0;
-    if (p.cm) {  // the packed weights stay [n][tap][cin]: same K-tile as ConvActDma
-      const int t = k0 / BK, j = t / 9;
-      k = (t - j * 9) * p.cin + j * BK;
-    }
-    koff = (uint32_t)k * 2u;
-  }
-  __device__ void one(const P&, const bf16_t* stage, int wid, int i) const {
-    dma16(rsrc, stage + (wid * NI + i) * 512, base[i] + koff);
-  }
-};
-
-// ---- KM loader (weight gradient): pixel rows of one operand -------------------
-template <int R>
-__device__ __forceinline__ int kmswz(int k) {
-  // 16-B chunk XOR for pixel row k of a [64][R] image (rows of 2R bytes)
-  if constexpr (2 * R >= 256) return 4 * (k & 3);
-  else if constexpr (2 * R == 128) return 4 * ((k >> 1) & 1);
-  else return 0;
-}
-
-template <int R, int NW, bool SHIFT, int BK = DBK>
-struct PixRowsDma {
-  static constexpr bool KM = true;
-  static constexpr int RB = 2 * R;                 // bytes per pixel row
-  static constexpr int NI = BK * RB / 1024 / NW;   // DMA instructions per wave and K-tile
-  static_assert(R >= 32 && NI >= 1 && NI * NW * 1024 == BK * RB, "dma shape");
-  using P = PixRowsPB;
-  __amdgpu_buffer_rsrc_t rsrc;
-  // per instruction: pixel row in the K-tile, channel, and (shifted operand)
-  // its tap: a tile may span several taps when R > Cin (meta = colok<<4 |
-  // (dy+1)<<2 | (dx+1))
-  int row[NI], cof[NI], meta[NI];
-  int base_pix, kend, k0;
-
-  __device__ void init(const P& p, int off, int kbeg, int kend_, int wid, int lane) {
-    kend = kend_;
-    base_pix = max(0, kbeg - p.W - 1);
-    rsrc = make_rsrc_b(p.x + (size_t)base_pix * p.ld, (long long)(p.M - base_pix) * p.ld);
-    const int taps = p.ksize * p.ksize;
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const int byte = (wid * NI + i) * 1024 + lane * 16;
-      const int k = byte / RB, pc = (byte % RB) / 16;
-      row[i] = k;
-      const int col = off + ((pc ^ kmswz<R>(k)) << 3);  // column of the GEMM's N (or M)
-      int tap = 0, c = col;
-      if (p.cin > 0) {
-        tap = col / p.cin;
-        c = col - tap * p.cin;
-      }
-      cof[i] = c;
-      int dy = 0, dx = 0;
-      if (SHIFT && p.ksize == 3) {
-        dy = tap / 3 - 1;
-        dx = tap % 3 - 1;
-      }
-      const bool ok = c < p.ncols && (p.cin == 0 || tap < taps);
-      meta[i] = (ok ? 16 : 0) | ((dy + 1) << 2) | (dx + 1);
-    }
-  }
-  __device__ void prep(const P&, int k0_) { k0 = k0_; }
-  __device__ void one(const P& p, const bf16_t* stage, int wid, int i) const {
-    const int q = k0 + row[i];
-    const int m = meta[i];
-    bool ok = (m >> 4) & (q < kend);
-    int src = q;
-    if constexpr (SHIFT) {
-      const int dy = ((m >> 2) & 3) - 1, dx = (m & 3) - 1;
-      const int t = (int)fdiv((uint32_t)q, p.fdW);
-      const int xx = q - t * p.W;
-      const int b = (int)fdiv((uint32_t)t, p.fdH);
-      const int yy = t - b * p.H;
-      ok = ok & ((unsigned)(yy + dy) < (unsigned)p.H) & ((unsigned)(xx + dx) < (unsigned)p.W);
-      src = q + dy * p.W + dx;
-    }
-    const uint32_t off = ((uint32_t)((src - base_pix) * p.ld + cof[i]) * 2u) | (ok ? 0u : OOB);
-    dma16(rsrc, stage + (wid * NI + i) * 512, off);
-  }
-};
-
-// one K-tile's DMA instruction j of this wave (A's first, then B's)
-template <class AL, class BL>
-__device__ __forceinline__ void dma_one(const AL& a, const BL& b, const typename AL::P& ap,
-                                        const typename BL::P& bp, const bf16_t* stage, int a_el,
-                                        int wid, int j) {
-  if (j < AL::NI) a.one(ap, stage, wid, j);
-  else b.one(bp, stage + a_el, wid, j - AL::NI);
-}
 
 // Fragment of k-step s (0..3), rows rb..rb+31 of the tile (lane & 31 selects
 // the row). MK: one plain ds_read_b128 (counted by hipcc). KM: two
@@ -273,13 +68,6 @@ struct FragRd {
     return __builtin_bit_cast(bf16x8, w);
   }
 };
-__device__ __forceinline__ void lgkm_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-template <int N>
-__device__ __forceinline__ void lgkm_fence_n() {
-  static_assert(N >= 0 && N <= 15, "lgkmcnt range");
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // 16x16x32 accumulators -> the 32x32 MFMA layout every epilogue reads.
 // 16x16 quadrant (a, b) lane l reg j holds C[16a + 4 (l >> 4) + j][16b + (l & 15)];
 // the 32x32 layout wants, at lane l reg i, C[(i & 3) + 8 (i >> 2) + 4 (l >> 5)][l & 31]:
@@ -879,44 +667,23 @@ __global__ void __launch_bounds__(512)
 // on the halo kernel, 2 = as 1 with 64-channel N tiles for the 256-wide
 // 128-channel layers. Measured slower than the im2col DMA GEMMs on every
 // layer of the B=64 step but conv4 (DESIGN.md, round 5), so off by default
-static int bf16_halo() {
-  const char* e = getenv("NSM_BF16_HALO");
-  return e ? atoi(e) : 0;
-}
+static int bf16_halo() { return (int)env_int("NSM_BF16_HALO", 0); }
 
 // NSM_BF16_DMA selects the pipelined kernels: 0 = off (register-staged
 // kernels only), 1 = 256x128 forward tiles only, 2 = 256x256 forward tiles
 // where Cout % 256 == 0 (default; measured 1142 vs 924 TFLOP/s on conv6)
-static int bf16_dma_mode() {
-  static int mode = [] {
-    const char* e = getenv("NSM_BF16_DMA");
-    return e ? atoi(e) : 2;
-  }();
-  return mode;
-}
+static int bf16_dma_mode() { static const int v = (int)env_int("NSM_BF16_DMA", 2); return v; }
 // NSM_BF16_XCD: bit 0 = XCD-contiguous tile order for the forward/dgrad DMA
 // GEMMs, bit 1 = for the weight-gradient DMA GEMMs
-static int bf16_xcd() {
-  static int v = [] {
-    const char* e = getenv("NSM_BF16_XCD");
-    // measured: fwd +-0 %, wgrad +0.4 % (r02); both, r04: B=64 step 1226 -> 1232
-    // frames/s, and the 4 N-tiles of an M block share one XCD's L2 (A fetched once)
-    return e ? atoi(e) : 3;
-  }();
-  return v;
-}
+// measured: fwd +-0 %, wgrad +0.4 % (r02); both, r04: B=64 step 1226 -> 1232
+// frames/s, and the 4 N-tiles of an M block share one XCD's L2 (A fetched once)
+static int bf16_xcd() { static const int v = (int)env_int("NSM_BF16_XCD", 3); return v; }
 // NSM_BF16_PF: bit 0 = fragment reads one k-step ahead (PF) in the forward /
 // dgrad DMA GEMMs, bit 1 = in the weight-gradient DMA GEMMs. Measured (B=64
 // bf16 train step, A/B in one box): off 1110-1113 frames/s, fwd+wgrad 1105-1106,
 // fwd 1104, wgrad 1110: two waves per SIMD already hide the LDS read latency,
 // so it stays off by default
-static int bf16_pf() {
-  static int v = [] {
-    const char* e = getenv("NSM_BF16_PF");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
+static int bf16_pf() { static const int v = (int)env_int("NSM_BF16_PF", 0); return v; }
 // NSM_BF16_DMA_PIPE: K-tile ring of the 256x256 forward / dgrad GEMMs:
 // 0 = BK 64 x 2 stages, 1 = BK 32 x 5 stages (all 160 KiB), 2 = BK 32 x 4,
 // 3 = BK 64 x 2 with the refill issued before the first LDS read. Measured
@@ -925,64 +692,29 @@ static int bf16_pf() {
 // ring does not pay: the per-K-tile barrier and the LDS-DMA issue cost (eight
 // 1-KiB pieces per wave per K-tile beside 32 MFMAs), not the DMA latency,
 // bound this loop
-static int bf16_dma_pipe() {
-  static int v = [] {
-    const char* e = getenv("NSM_BF16_DMA_PIPE");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
+static int bf16_dma_pipe() { static const int v = (int)env_int("NSM_BF16_DMA_PIPE", 0); return v; }
 // NSM_BF16_ILV: refill pieces placed between the MFMAs of each k-step
 // (REFILL 2) instead of behind its fragment reads: bit 0 forward / dgrad,
 // bit 1 weight gradient. Measured (B=64 bf16 train step, A/B in one box):
 // off 1101-1109 frames/s, both 1062-1076, forward only 1099, weight gradient
 // only 1081: off by default
-static int bf16_ilv() {
-  static int v = [] {
-    const char* e = getenv("NSM_BF16_ILV");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
+static int bf16_ilv() { static const int v = (int)env_int("NSM_BF16_ILV", 0); return v; }
 // NSM_BF16_XT=0: the 2-stage forward / dgrad DMA GEMMs on the per-tile
 // barrier loop instead of the cross-tile pipeline (REFILL 3). Measured (B=64
 // bf16, A/B in one box): conv6 fwd GEMM 1200 -> 1226 TFLOP/s, train step
 // 1166-1170 -> 1173-1175 frames/s
-static bool bf16_xt() {
-  static bool v = [] {
-    const char* e = getenv("NSM_BF16_XT");
-    return !e || atoi(e) != 0;
-  }();
-  return v;
-}
+static bool bf16_xt() { static const bool v = env_flag("NSM_BF16_XT", true); return v; }
 // NSM_BF16_XT_WG: the 2-stage weight-gradient DMA GEMMs on the cross-tile
 // pipeline. Measured (B=64 bf16, A/B in one box): 1181-1185 off vs 1176-1184
 // frames/s on (conv8/conv9 -1 %, conv6/conv7 +1 %): off by default
-static bool bf16_xt_wg() {
-  static bool v = [] {
-    const char* e = getenv("NSM_BF16_XT_WG");
-    return e && atoi(e) != 0;
-  }();
-  return v;
-}
+static bool bf16_xt_wg() { static const bool v = env_flag("NSM_BF16_XT_WG", false); return v; }
 // NSM_BF16_KORDER=0: tap-major K walk for the DMA 3x3 convolutions
-static bool bf16_korder() {
-  static bool v = [] {
-    const char* e = getenv("NSM_BF16_KORDER");
-    return !e || atoi(e) != 0;
-  }();
-  return v;
-}
+static bool bf16_korder() { static const bool v = env_flag("NSM_BF16_KORDER", true); return v; }
 // NSM_BF16_MF16=1: the 2-stage forward / dgrad DMA GEMMs on
 // v_mfma_f32_16x16x32_bf16 (REFILL 4) instead of 32x32x16 (REFILL 3);
 // =2: only the 256x256 tiles with K >= 4096 (conv6 / conv7 3x3)
-static int bf16_mf16() {
-  static int v = [] {
-    const char* e = getenv("NSM_BF16_MF16");
-    return e ? atoi(e) : 2;  // measured: 0 1193-1201, 2 1202-1205 frames/s (B=64 step)
-  }();
-  return v;
-}
+// measured: 0 1193-1201, 2 1202-1205 frames/s (B=64 step)
+static int bf16_mf16() { static const int v = (int)env_int("NSM_BF16_MF16", 2); return v; }
 template <int BM, int BN, int WM, int WN, int STAGES, int BK, int REFILL, class EP = EpiStoreB>
 static int launch_conv_fwd_dma_v(const ConvActPB& ap, const RowsKPB& bp, const typename EP::P& ep,
                                  int M, int N, int K, hipStream_t s) {

@@ -1,6 +1,7 @@
 // fp32 GEMMs on the bf16 matrix cores: exact three-way split (bf16x6).
-// Included in nsm_conv.hip after the fp32 GEMM kernel (uses its loaders and
-// epilogues); also holds the bf16 operand-image helpers nsm_conv_bf16.inc uses.
+// gemm_f32s_kernel, templated on the fp32 kernel's loaders and epilogues.
+// Included at the top of nsm_conv.hip only (after nsm_conv.h), which
+// instantiates and launches it (launch_f32_gemm).
 //
 // Each fp32 operand x is written as x = h + m + l with h = bf16(x),
 // m = bf16(x - h), l = bf16(x - h - m) (round to nearest even). The splits
@@ -23,36 +24,8 @@
 //   KM [plane][32][KMS]: the bf16 weight-gradient image (KMStride), read
 //       with ds_read_b64_tr_b16 (read_frag_b<true>).
 
-// ---- bf16 operand images (shared with nsm_conv_bf16.inc) --------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-constexpr int BKB = 64;
-constexpr int LDKB = BKB + 8;
-
-template <int R>
-struct KMStride {  // bf16 elements per KM row: (row dwords) = 16 (mod 32)
-  static constexpr int value = R == 32 ? 96 : R + 32;
-};
-
-// fragment of k-step s (0..3) for rows rb..rb+31 of the tile
-template <bool KM, int R>
-__device__ __forceinline__ bf16x8 read_frag_b(const bf16_t* S, int rb, int lane, int s) {
-  if constexpr (!KM) {
-    const int r = lane & 31, h = lane >> 5;
-    return __builtin_bit_cast(bf16x8, *(const u32x4*)&S[(rb + r) * LDKB + 16 * s + 8 * h]);
-  } else {
-    constexpr int KMS = KMStride<R>::value;
-    const int h = lane >> 5, g16 = (lane >> 4) & 1, q = (lane >> 2) & 3, p = lane & 3;
-    const bf16_t* a = S + (16 * s + 8 * h + q) * KMS + rb + 16 * g16 + 4 * p;
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)a);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a + 4 * KMS));
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    s16x8 v = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    return __builtin_bit_cast(bf16x8, v);
-  }
-}
+// bf16x8, BKB, LDKB, KMStride, read_frag_b, xcd_block_order: nsm_conv.h
+namespace nsm {
 
 __device__ __forceinline__ void split4(f32x4 v, u32x2& h, u32x2& m, u32x2& l) {
   h = u32x2{pack_bf2(v.x, v.y), pack_bf2(v.z, v.w)};
@@ -100,27 +73,6 @@ __device__ __forceinline__ void split_store(const L& ld, bf16_t* S, const f32x4*
 #pragma unroll
     for (int i = 0; i < L::NPT; ++i) I::put(S, ld.c4o, ld.krow0 + i * L::KSTEP, r[i]);
   }
-}
-
-// XCD-aware block order: blocks are dealt round-robin over the 8 XCDs, so
-// dispatch slot L runs on XCD L % 8; slot L becomes logical block
-// (L % 8) * (total / 8) + L / 8, each XCD a contiguous range of them, so the
-// blocks that share an operand tile share one L2. mode 1: M-blocks fastest
-// (batched / split-K grids: whole Winograd components / K-splits per XCD);
-// mode 2: N-blocks fastest (2-D grids: the N-blocks reading one activation
-// panel run together on one XCD, which then fetches the panel once)
-__device__ __forceinline__ void xcd_block_order(int& bx, int& by, int& bz, int mode) {
-  const unsigned gx = gridDim.x, gy = gridDim.y, total = gx * gy * gridDim.z;
-  const unsigned L = bx + gx * (by + gy * bz);
-  const unsigned lg = (L & 7) * (total >> 3) + (L >> 3);
-  if (mode == 2) {
-    by = lg % gy;
-    bx = (lg / gy) % gx;
-  } else {
-    bx = lg % gx;
-    by = (lg / gx) % gy;
-  }
-  bz = lg / (gx * gy);
 }
 
 // MFMAs of one 16-deep K-step on the split fragments (smallest terms first)
@@ -230,72 +182,4 @@ __global__ void __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_
   EP::template apply<TM, TN, WM, WN>(ep, acc, cx, M, N, split);
 }
 
-#include "nsm_conv_split16.inc"
-
-// ---- host side ---------------------------------------------------------------
-// fp32 GEMM arithmetic: 0 = fp32 MFMA, 1 = bf16 three-way split, 2 = the
-// f16x2 split where the caller passes the operands' maxima (bf16 split
-// elsewhere). -1: not set yet (env NSM_F32_SPLIT, default 2);
-// nsm_set_f32_split overrides.
-static int g_f32_split = -1;
-static int f32_split_mode() {
-  if (g_f32_split < 0) {
-    const char* e = getenv("NSM_F32_SPLIT");
-    const int v = e ? atoi(e) : 2;
-    g_f32_split = v < 0 ? 0 : (v > 2 ? 2 : v);
-  }
-  return g_f32_split;
-}
-static bool f32_split() { return f32_split_mode() != 0; }
-
-// NSM_SPLIT_XCD=0: dispatch order as launched (no XCD-contiguous remap)
-static bool split_xcd() {
-  static bool v = [] {
-    const char* e = getenv("NSM_SPLIT_XCD");
-    return !e || atoi(e) != 0;
-  }();
-  return v;
-}
-
-// NSM_F32_XCD2D=1: 2-D fp32 GEMM grids with several N-blocks in the
-// N-fastest XCD order (the N-blocks of one activation panel on one XCD).
-// Measured (B=8 fp32 step, 2 runs each, one box): 636.8 / 638.3 off, 628.4 /
-// 638.6 frames/s on — no gain, off by default.
-static bool f32_xcd2d() {
-  static bool v = [] {
-    const char* e = getenv("NSM_F32_XCD2D");
-    return e && atoi(e) != 0;
-  }();
-  return v;
-}
-
-// the fp32 GEMM launch of every fp32 conv: split kernel or fp32 MFMA kernel.
-// amax (device bits of max|A|, max|B|) selects the f16x2 split
-// (nsm_conv_split16.inc) where the caller has the operands' maxima.
-template <int BM, int BN, int WM, int WN, class AL, class BL, class EP, class AP, class BP>
-static void launch_f32_gemm(dim3 grid, hipStream_t s, const AP& ap, const BP& bp,
-                            const typename EP::P& ep, int M, int N, int K, int kchunk, int zsplit,
-                            AmaxPair amax = AmaxPair{nullptr, nullptr});
-
-template <int BM, int BN, int WM, int WN, class AL, class BL, class EP, class AP, class BP>
-static void launch_f32_gemm(dim3 grid, hipStream_t s, const AP& ap, const BP& bp,
-                            const typename EP::P& ep, int M, int N, int K, int kchunk, int zsplit,
-                            AmaxPair amax) {
-  constexpr int NT = WM * WN * 64;
-  // remap batched / split-K grids (M fastest) and 2-D grids with several
-  // N-blocks (N fastest, NSM_F32_XCD2D) whose block count the 8 XCDs divide
-  const long long total = (long long)grid.x * grid.y * grid.z;
-  const int remap = !split_xcd() || total % 8 != 0 ? 0
-                    : grid.z > 1                   ? 1
-                    : grid.y > 1 && f32_xcd2d()   ? 2
-                                                   : 0;
-  if (amax.on() && f32_split_mode() == 2)
-    hipLaunchKernelGGL((gemm_f32h_kernel<BM, BN, WM, WN, AL, BL, EP, AP, BP>), grid, dim3(NT), 0,
-                       s, ap, bp, ep, M, N, K, kchunk, zsplit, remap, amax);
-  else if (f32_split())
-    hipLaunchKernelGGL((gemm_f32s_kernel<BM, BN, WM, WN, AL, BL, EP, AP, BP>), grid, dim3(NT), 0,
-                       s, ap, bp, ep, M, N, K, kchunk, zsplit, remap);
-  else
-    hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, AL, BL, EP, AP, BP>), grid, dim3(NT), 0, s,
-                       ap, bp, ep, M, N, K, kchunk, zsplit);
-}
+}  // namespace nsm

@@ -1,6 +1,6 @@
 // fp32 GEMMs on the f16 matrix cores: two-term fp16 split of power-of-two
-// scaled operands (f16x2). Included in nsm_conv.hip after nsm_conv_split.inc
-// (shares its loaders, LDS layouts and epilogues).
+// scaled operands (f16x2). Included at the top of nsm_conv.hip only, after
+// nsm_conv_split.inc (shares its LDS layouts).
 //
 // Each fp32 operand tensor X gets one power-of-two scale s = 2^(15 - e),
 // e = ceil(log2 max|X|), from the absolute maximum its producer recorded
@@ -21,7 +21,7 @@
 // Non-finite operands: max|X| = Inf/NaN gives s = 1, and h = Inf makes the
 // residual NaN, so the outputs they touch are NaN (as under the bf16 split).
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+namespace nsm {
 
 // where a GEMM's operands keep their absolute maxima (slots of NSM_AMAX_WORDS)
 struct AmaxPair {
@@ -163,41 +163,6 @@ __global__ void __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_
   EP::template apply<TM, TN, WM, WN>(ep, acc, cx, M, N, split);
 }
 
-// max|x| over n floats -> atomic max into the bits at *out (zero it first):
-// the scale source of a GEMM operand whose producer does not record it
-__global__ void __launch_bounds__(256) absmax_kernel(const float* __restrict__ x, long long n,
-                                                     uint32_t* __restrict__ out) {
-  uint32_t m = 0;
-  const long long n4 = n >> 2;
-  const f32x4* x4 = (const f32x4*)x;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4;
-       i += (long long)gridDim.x * 256)
-    amax_fold(m, x4[i]);
-  for (long long i = (n4 << 2) + (long long)blockIdx.x * 256 + threadIdx.x; i < n;
-       i += (long long)gridDim.x * 256)
-    amax_fold(m, x[i]);
-  amax_flush(m, out);
-}
-
-// the same over bf16 words (a bf16 value's magnitude bits are the top half of
-// its fp32 widening): 8 values per 16-B load
-__global__ void __launch_bounds__(256) absmax_bf16_kernel(const bf16_t* __restrict__ x, long long n,
-                                                          uint32_t* __restrict__ out) {
-  uint32_t m = 0;
-  const long long n8 = n >> 3;
-  const u32x4* x8 = (const u32x4*)x;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n8;
-       i += (long long)gridDim.x * 256) {
-    const u32x4 w = x8[i];
-    amax_fold(m, f32x4{bf_lo(w.x), bf_hi(w.x), bf_lo(w.y), bf_hi(w.y)});
-    amax_fold(m, f32x4{bf_lo(w.z), bf_hi(w.z), bf_lo(w.w), bf_hi(w.w)});
-  }
-  for (long long i = (n8 << 3) + (long long)blockIdx.x * 256 + threadIdx.x; i < n;
-       i += (long long)gridDim.x * 256)
-    amax_fold(m, __uint_as_float((uint32_t)x[i] << 16));
-  amax_flush(m, out);
-}
-
 // ---- pre-split (h2) operands: H2Scale, h2_exp, h2_store4 (nsm_common.h) ----
 // h2 words of two consecutive channels held by lanes (2i, 2i+1): the even lane
 // stores the pair's h terms, the odd lane the pair's l terms, one 4-B store
@@ -217,3 +182,5 @@ __device__ __forceinline__ int h2_pair_off(int c) {
   const int c0 = c & ~1;
   return 16 * (c0 >> 3) + (c0 & 7) + ((c & 1) ? 8 : 0);
 }
+
+}  // namespace nsm

@@ -1441,20 +1441,11 @@ struct SepPlan {
 // elem_bench_f32.py, B=8 fp32): R = 2 vs 1 cuts the x2 backward 126 -> 110 us
 // (C=512), and R = 4 is no faster without the fused BN reduction and slower
 // with it (124 -> 145 us: four partial-row reductions per block)
-static int sep_rmax() {
-  static int v = [] {
-    const char* e = getenv("NSM_SEP_RMAX");
-    return e ? atoi(e) : 2;
-  }();
-  return v;
-}
+static int sep_rmax() { static const int v = (int)env_int("NSM_SEP_RMAX", 2); return v; }
 // NSM_SEP_LDS_KB: the LDS budget of the backward's fp32 row sums per block
 // (64 KiB: two blocks per CU; 16 / 32 measured slower, B=8 fp32 step)
 static size_t sep_lds_budget() {
-  static size_t v = [] {
-    const char* e = getenv("NSM_SEP_LDS_KB");
-    return (size_t)(e ? atoi(e) : 64) * 1024;
-  }();
+  static const size_t v = (size_t)(int)env_int("NSM_SEP_LDS_KB", 64) * 1024;
   return v;
 }
 static SepPlan sep_bwd_plan(int C, int tw) {
@@ -1511,13 +1502,7 @@ static void dispatch_sep_bwd(const SepPlan& pl, int B, size_t lds, hipStream_t s
 // 366 vs 541 us; 1080p eval 505 vs 457 frames/s)
 // (NSM_RESIZE_SEP=2: the separable forms for the 16-bit storage too; measured
 // slower again in round 6: B=64 bf16 x2 backward 516 -> 773 us at conv8)
-static int sep_resize_mode() {
-  static int v = [] {
-    const char* e = getenv("NSM_RESIZE_SEP");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
-}
+static int sep_resize_mode() { static const int v = (int)env_int("NSM_RESIZE_SEP", 1); return v; }
 static bool sep_resize() { return sep_resize_mode() != 0; }
 static bool sep_for(int dtype) { return dtype == NSM_F32 ? sep_resize() : sep_resize_mode() == 2; }
 
@@ -2289,13 +2274,7 @@ extern "C" int nsm_avgpool2_bwd_add(const void* dy, int B, int H, int W, int C, 
 }
 
 // NSM_RESIZE_ROWS=0: per-element resize backward instead of the row-blocked one
-static bool rows_resize() {
-  static bool v = [] {
-    const char* e = getenv("NSM_RESIZE_ROWS");
-    return !e || atoi(e) != 0;
-  }();
-  return v;
-}
+static bool rows_resize() { static const bool v = env_flag("NSM_RESIZE_ROWS", true); return v; }
 
 // 8-channel path when C % 8 == 0 (all model activations), scalar otherwise
 #define NSM_DT(KER, ...)                                                        \

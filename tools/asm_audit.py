@@ -17,7 +17,7 @@ CSRC = os.path.join(ROOT, "pcss-unet_amd", "csrc")
 
 def main():
     pat = sys.argv[1] if len(sys.argv) > 1 else "dma"
-    src = sys.argv[2] if len(sys.argv) > 2 else "nsm_conv.hip"
+    src = sys.argv[2] if len(sys.argv) > 2 else "nsm_conv_bf16.hip"
     out = "/tmp/nsm_asm"
     os.makedirs(out, exist_ok=True)
     subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950",
