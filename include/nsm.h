@@ -603,6 +603,24 @@ int nsm_detail_loss_fwd(const float* o, const float* t, int B, int H, int W, flo
 int nsm_detail_loss_bwd(const float* o, const float* t, int B, int H, int W, float w_hf,
                         float w_pen, float w_sob, const float* mcount, const float* gscale,
                         float* grad, int accumulate, void* stream);
+/* The SSIM term of CustomLoss (customLoss.py:187-191: 1 - pytorch_msssim.ssim)
+ * and the SSIM metric on o, t [B,1,H,W] fp32: 11-tap Gaussian window (sigma
+ * 1.5), valid correlation ((H-10) x (W-10) windows per image), C1 = (0.01 R)^2,
+ * C2 = (0.03 R)^2 with R = data_range (> 0), no clamp; ssim = the mean over the
+ * batch of the per-image means. nsm_ssim_blocks: 0 for an unsupported shape
+ * (B <= 0, H or W below 11).
+ * fwd: partial holds nsm_ssim_blocks(B,H,W) floats; out[3 + B] = ssim,
+ *   1 - ssim, (base ? *base : 0) + w * (1 - ssim), then ssim of each image.
+ *   coef (may be NULL: metric only) receives the per-window partials of S that
+ *   the backward reads: 3 * B*(H-10)*(W-10) floats. No atomics.
+ * bwd: grad (+)= d(w * (1 - ssim))/do * (*gscale) from o, t and the forward's
+ *   coef; gscale: device scalar (NULL: 1) as in nsm_l1_loss_bwd; accumulate != 0
+ *   adds into grad; w == 0 contributes exactly 0. One writer per element. */
+int nsm_ssim_blocks(int B, int H, int W);
+int nsm_ssim_fwd(const float* o, const float* t, int B, int H, int W, float data_range, float w,
+                 const float* base, float* partial, float* coef, float* out, void* stream);
+int nsm_ssim_bwd(const float* o, const float* t, const float* coef, int B, int H, int W, float w,
+                 const float* gscale, float* grad, int accumulate, void* stream);
 /* PerturbationLoss.perturb_input (pert_loss.py:26-59):
  * per-channel unbiased std over the batch of NCHW x -> std[C] */
 int nsm_channel_std(const float* x, int B, int C, int H, int W, float* partial, float* std,

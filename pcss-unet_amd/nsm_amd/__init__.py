@@ -7,7 +7,8 @@ Importing this package loads libnsm.so and fails loudly if it is missing.
 from ._lib import LIB_PATH, NsmError, lib  # noqa: F401  (loads the HIP library)
 from .unet import DoubleConv, Unet, reserve_side_stream  # noqa: F401
 from .losses import (CustomLoss, EnhancedCustomLoss, L1Loss, PerturbationLoss,  # noqa: F401
-                     detail_loss, detail_terms, l1_loss, measure_temporal_instability)
+                     detail_loss, detail_terms, l1_loss, measure_temporal_instability, ssim,
+                     ssim_loss)
 from .optim import (FlatAdam, FlatAdamW, FlatSGD, allreduce_grads, flat_grad,  # noqa: F401
                     make_optimizer)
 from .infer import GraphedUnet  # noqa: F401

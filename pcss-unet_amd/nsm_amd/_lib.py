@@ -126,6 +126,9 @@ _SIGS = {
     "nsm_detail_blocks": (I, [I, I, I]),
     "nsm_detail_loss_fwd": (I, [P, P, I, I, I, F, F, F, P, P, P, P]),
     "nsm_detail_loss_bwd": (I, [P, P, I, I, I, F, F, F, P, P, P, I, P]),
+    "nsm_ssim_blocks": (I, [I, I, I]),
+    "nsm_ssim_fwd": (I, [P, P, I, I, I, F, F, P, P, P, P, P]),
+    "nsm_ssim_bwd": (I, [P, P, P, I, I, I, F, P, P, I, P]),
     "nsm_channel_std": (I, [P, I, I, I, I, P, P, P]),
     "nsm_perturb": (I, [P, P, P, I, I, I, I, F, P, P]),
     "nsm_sumsq": (I, [P, L, P, P, P]),

@@ -26,6 +26,22 @@
   and the Sobel-magnitude L1, fused in nsm_detail_loss_fwd/bwd; still one
   autograd node and one gradient buffer. [B,1,H,W] only (ValueError otherwise).
   `detail_terms(output, target)` returns the three terms as device scalars.
+  `ssim_weight` (opt-in, default 0: every path above, unchanged) adds the
+  reference's commented-out structural-similarity term (customLoss.py:187-191,
+  `1 - pytorch_msssim.ssim(output, target)`, weight 0.1 there):
+  final = enhanced + ssim_weight*(1 - ssim), fused in nsm_ssim_fwd/bwd; one
+  autograd node and one gradient buffer with every combination of `vgg_grad`,
+  `detail_weight` and `gradient_weight` (backward order: VGG chain, L1, detail,
+  SSIM). `ssim_data_range` (default 1.0, the range of the sigmoid output) is
+  pytorch_msssim's `data_range`; the reference's literal call passes none and
+  would have used that package's default 255, which on [0, 1] images makes the
+  term almost constant (1 - ssim of the order 1e-5): `ssim_data_range=255.0`
+  reproduces it. [B,1,H,W] with H, W >= 11 only (ValueError otherwise).
+* `ssim(output, target, data_range=1.0, size_average=True)`: pytorch_msssim.ssim
+  with its defaults (11-tap Gaussian window, sigma 1.5, K = (0.01, 0.03), valid
+  windows, no clamp) as a detached device scalar, or the per-image [B] tensor
+  with `size_average=False`; no host synchronisation. `ssim_loss(output,
+  target, data_range=1.0)` is 1 - ssim, differentiable wrt `output`.
 * The reference asserts `output.min() >= 0 and output.max() <= 1`
   (customLoss.py:131) with a host sync per call. Here a range-check kernel
   sets a sticky device flag that is copied to pinned host memory
@@ -45,6 +61,8 @@
   training]. `detail_weight` / `gradient_weight` as in CustomLoss: when one
   is non-zero the detail terms join `total` and the dict gains
   'high_freq_loss', 'penumbra_loss' and 'gradient_loss' (device scalars).
+  `ssim_weight` / `ssim_data_range` as in CustomLoss: with the weight on the
+  term joins `total` and the dict gains 'ssim_loss' = 1 - ssim (device scalar).
 * `measure_temporal_instability(frames, motion_vectors=None, alpha=5.0)`:
   pert_loss.py:166-199, mean over consecutive frame pairs of
   mean(exp(alpha*|f_t - f_{t-1}|) - 1) (`nsm_expdiff_mean`).
@@ -314,6 +332,139 @@ class _CustomDetailFn(torch.autograd.Function):
         return grad.view(ctx.oshape), None, None, None, None, None, None
 
 
+def _ssim_inputs(o, t):
+    """[B,1,H,W] fp32 contiguous output and target, H and W at least the window."""
+    require_gpu(o, "ssim input")
+    if o.dim() != 4 or o.shape[1] != 1:
+        raise ValueError(f"ssim: expected a [B,1,H,W] output, got {tuple(o.shape)}")
+    if tuple(t.shape) != tuple(o.shape):
+        raise ValueError(f"ssim: shape mismatch {tuple(o.shape)} vs {tuple(t.shape)}")
+    if o.shape[2] < 11 or o.shape[3] < 11:
+        raise ValueError(f"ssim: H and W must be at least the 11-pixel window, got "
+                         f"{tuple(o.shape)}")
+    o_ = o.detach().contiguous().to(torch.float32)
+    t_ = t.detach().contiguous().to(device=o.device, dtype=torch.float32)
+    return o_, t_
+
+
+def _ssim_fwd(o_, t_, data_range, w=0.0, base=None, keep=False):
+    """The fused forward: a device vector (ssim, 1 - ssim, base + w*(1 - ssim),
+    ssim of each image) and, with `keep`, the coefficient planes of the backward."""
+    B, _, H, W = o_.shape
+    nb = lib.nsm_ssim_blocks(B, H, W)
+    if nb <= 0 or not data_range > 0:
+        raise ValueError(f"ssim: unsupported shape {tuple(o_.shape)} or data_range {data_range}")
+    partial = torch.empty(nb, dtype=torch.float32, device=o_.device)
+    vec = torch.empty(3 + B, dtype=torch.float32, device=o_.device)
+    coef = (torch.empty(3 * B * (H - 10) * (W - 10), dtype=torch.float32, device=o_.device)
+            if keep else None)
+    call("nsm_ssim_fwd", ptr(o_), ptr(t_), B, H, W, float(data_range), float(w), ptr(base),
+         ptr(partial), ptr(coef), ptr(vec), stream())
+    return vec, coef
+
+
+def _ssim_bwd(o_, t_, coef, w, g_, grad, accumulate):
+    B, _, H, W = o_.shape
+    call("nsm_ssim_bwd", ptr(o_), ptr(t_), ptr(coef), B, H, W, float(w), ptr(g_), ptr(grad),
+         int(accumulate), stream())
+
+
+def ssim(output, target, data_range=1.0, size_average=True):
+    """pytorch_msssim.ssim(output, target, data_range) with its other defaults
+    on [B,1,H,W] images, as a detached device scalar ([B] per-image values with
+    size_average=False), without a host synchronisation. `data_range` defaults
+    to 1.0 (sigmoid outputs), not to pytorch_msssim's 255."""
+    o_, t_ = _ssim_inputs(output, target)
+    vec, _ = _ssim_fwd(o_, t_, data_range)
+    return vec[0] if size_average else vec[3:]
+
+
+class _SsimFn(torch.autograd.Function):
+    """weight * (1 - ssim) as one node; also returns 1 - ssim (detached)."""
+
+    @staticmethod
+    def forward(ctx, o, t, weight, data_range):
+        o_, t_ = _ssim_inputs(o, t)
+        ctx.w = float(weight)
+        vec, coef = _ssim_fwd(o_, t_, data_range, ctx.w, keep=True)
+        ctx.save_for_backward(o_, t_, coef)
+        ctx.oshape = o.shape
+        ctx.set_materialize_grads(False)   # no zero-filled gradient for the term
+        term = vec[1]
+        ctx.mark_non_differentiable(term)
+        return vec[2], term
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        o_, t_, coef = ctx.saved_tensors
+        grad = torch.empty_like(o_)
+        g_ = g.detach().contiguous().to(torch.float32)
+        _ssim_bwd(o_, t_, coef, ctx.w, g_, grad, False)
+        return grad.view(ctx.oshape), None, None, None
+
+
+def ssim_loss(output, target, data_range=1.0):
+    """1 - ssim(output, target, data_range), differentiable wrt `output` on the
+    fused kernels (the term of customLoss.py:187-191)."""
+    return _SsimFn.apply(output, target, 1.0, data_range)[0]
+
+
+class _CustomSsimFn(torch.autograd.Function):
+    """CustomLoss with an SSIM weight: enhanced + ssim_weight*(1 - ssim)
+    (customLoss.py:187-191) as ONE node with one gradient tensor. enhanced is
+    _CustomDetailFn's value (base when both detail weights are 0). Backward:
+    the VGG chain (if any), nsm_l1_loss_bwd, nsm_detail_loss_bwd (if on), then
+    nsm_ssim_bwd accumulate into the same buffer."""
+
+    @staticmethod
+    def forward(ctx, o, t, alpha, vgg, vgg_value, detail_weight, gradient_weight, ssim_weight,
+                data_range):
+        from . import ops
+        o_, t_ = _ssim_inputs(o, t)
+        n = o_.numel()
+        partial = torch.empty(lib.nsm_loss_blocks(n), dtype=torch.float32, device=o_.device)
+        base = torch.empty((), dtype=torch.float32, device=o_.device)
+        call("nsm_l1_loss_fwd", ptr(o_), ptr(t_), n, float(alpha), ptr(partial), ptr(base),
+             stream())
+        ctx.acts = None
+        if vgg is not None:
+            with ops.stage("vgg.fwd"):
+                v, ctx.acts = vgg._forward(o_, t_, keep=True)
+            base = base + (1 - alpha) * v            # the arithmetic of _CustomVggFn
+        elif vgg_value is not None:
+            base = base + (1 - alpha) * vgg_value    # the arithmetic of the detached default
+        ctx.w = (float(detail_weight), float(detail_weight), float(gradient_weight))
+        ctx.detail = detail_weight != 0.0 or gradient_weight != 0.0
+        dvec = None
+        if ctx.detail:
+            dvec = _detail_fwd(o_, t_, *ctx.w, base=base)
+            base = dvec[4]
+        ctx.ws = float(ssim_weight)
+        vec, coef = _ssim_fwd(o_, t_, data_range, ctx.ws, base=base, keep=True)
+        ctx.save_for_backward(o_, t_, coef, dvec)
+        ctx.vgg, ctx.alpha, ctx.oshape = vgg, float(alpha), o.shape
+        term = vec[1]
+        ctx.mark_non_differentiable(term)
+        ctx.set_materialize_grads(False)
+        return vec[2], term
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        from . import ops
+        o_, t_, coef, dvec = ctx.saved_tensors
+        grad = torch.empty_like(o_)
+        g_ = g.detach().contiguous().to(torch.float32)
+        if ctx.vgg is not None:
+            with ops.stage("vgg.bwd"):
+                ctx.vgg._backward(ctx.acts, o_, g_, grad, scale=1 - ctx.alpha)
+        call("nsm_l1_loss_bwd", ptr(o_), ptr(t_), o_.numel(), ctx.alpha, ptr(g_), ptr(grad),
+             1 if ctx.vgg is not None else 0, stream())
+        if ctx.detail:
+            _detail_bwd(o_, t_, ctx.w, dvec, g_, grad, True)
+        _ssim_bwd(o_, t_, coef, ctx.ws, g_, grad, True)
+        return (grad.view(ctx.oshape),) + (None,) * 8
+
+
 class L1Loss(nn.Module):
     def forward(self, output, target):
         return l1_loss(output, target)
@@ -321,13 +472,16 @@ class L1Loss(nn.Module):
 
 class CustomLoss(nn.Module):
     def __init__(self, device=None, alpha=0.9, vgg=None, vgg_weights="auto", check_range=True,
-                 vgg_grad=False, detail_weight=0.0, gradient_weight=0.0):
+                 vgg_grad=False, detail_weight=0.0, gradient_weight=0.0, ssim_weight=0.0,
+                 ssim_data_range=1.0):
         super().__init__()
         self.alpha = alpha
         self.l1 = L1Loss()
         self.vgg_grad = bool(vgg_grad)
         self.detail_weight = float(detail_weight)
         self.gradient_weight = float(gradient_weight)
+        self.ssim_weight = float(ssim_weight)
+        self.ssim_data_range = float(ssim_data_range)
         if self.vgg_grad and vgg is not None:
             raise ValueError("CustomLoss(vgg_grad=True) differentiates nsm_amd's own VGG stack: "
                              "it cannot be combined with a user-supplied vgg=<callable>")
@@ -368,6 +522,14 @@ class CustomLoss(nn.Module):
         if self.check_range:
             require_gpu(output, "CustomLoss output")
             self._range.launch(output.detach().contiguous().to(torch.float32))
+        if self.ssim_weight != 0.0:
+            v = None
+            if not self.vgg_grad and self.vgg is not None:
+                v = torch.as_tensor(self.vgg(output, target), device=output.device).detach()
+            return _CustomSsimFn.apply(output, target, self.alpha,
+                                       self.vgg_loss if self.vgg_grad else None, v,
+                                       self.detail_weight, self.gradient_weight,
+                                       self.ssim_weight, self.ssim_data_range)[0]
         if self.detail_weight != 0.0 or self.gradient_weight != 0.0:
             v = None
             if not self.vgg_grad and self.vgg is not None:
@@ -433,7 +595,8 @@ class PerturbationLoss(nn.Module):
 
 class EnhancedCustomLoss(nn.Module):
     def __init__(self, device=None, alpha=0.9, perturb_weight=0.5, vgg=None, vgg_weights="auto",
-                 vgg_grad=False, detail_weight=0.0, gradient_weight=0.0):
+                 vgg_grad=False, detail_weight=0.0, gradient_weight=0.0, ssim_weight=0.0,
+                 ssim_data_range=1.0):
         super().__init__()
         self.alpha = alpha
         self.perturb_weight = perturb_weight
@@ -441,8 +604,11 @@ class EnhancedCustomLoss(nn.Module):
         self.vgg_grad = bool(vgg_grad)
         self.detail_weight = float(detail_weight)
         self.gradient_weight = float(gradient_weight)
+        self.ssim_weight = float(ssim_weight)
+        self.ssim_data_range = float(ssim_data_range)
         self.base = CustomLoss(device, alpha, vgg=vgg, vgg_weights=vgg_weights, vgg_grad=vgg_grad,
-                               detail_weight=detail_weight, gradient_weight=gradient_weight)
+                               detail_weight=detail_weight, gradient_weight=gradient_weight,
+                               ssim_weight=ssim_weight, ssim_data_range=ssim_data_range)
         self.vgg_loss = getattr(self.base, "vgg_loss", None) or vgg
         self.perturbation_loss = PerturbationLoss()
 
@@ -475,6 +641,11 @@ class EnhancedCustomLoss(nn.Module):
                                               self.detail_weight, self.gradient_weight)
             basic = basic + d
             losses.update(high_freq_loss=hf, penumbra_loss=pen, gradient_loss=sob)
+        if self.ssim_weight != 0.0:
+            # customLoss.py:187-191, its own node beside the L1 one
+            s, term = _SsimFn.apply(output, target, self.ssim_weight, self.ssim_data_range)
+            basic = basic + s
+            losses["ssim_loss"] = term
         if self.training and self.perturb_weight > 0:
             pert = self.perturbation_loss(model, inputs, output, noises=noises)
             total = basic + self.perturb_weight * pert
