@@ -339,3 +339,73 @@ def test_frame_loader_matches_dataset(device, tmp_path):
             assert x.requires_grad and x.shape[0] == len(idx)
             assert torch.allclose(x.detach().cpu(), ref_x, rtol=1e-6, atol=1e-6)
             assert torch.equal(y.cpu(), ref_y)
+
+
+# ---- eval epilogues at model level ---------------------------------------------
+EVAL_FIXTURES = ["eval_c4_b2_64", "eval_c7_b1_odd_41x73"]
+
+
+def _oracle_eval(np_sd, running, x_np, autocast):
+    """O.forward in eval mode on the calibrated state, in fp32 or under CPU autocast."""
+    sd = O.torch_state(np_sd)
+    sd.update({k: torch.from_numpy(v.copy()) for k, v in running.items()})
+    with torch.no_grad(), torch.autocast("cpu", dtype=autocast or torch.bfloat16,
+                                        enabled=autocast is not None):
+        out, _ = O.forward(sd, torch.from_numpy(x_np), training=False)
+    return out.float().numpy()
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "f16"])
+@pytest.mark.parametrize("name", EVAL_FIXTURES)
+def test_eval_fixture_calibrated_16bit(device, name, dtype):
+    """The eval fixtures WITH their calibrated running statistics in bf16 and
+    f16 storage (the other 16-bit eval tests run on mean 0 / variance 1, where
+    a wrong sign of mean * scale or a dropped shift in a 16-bit epilogue does
+    not show): against the fixture, within 1.5x of the reference's own
+    deviation under CPU autocast of that dtype (same state, same input; the
+    margin of test_train_fixture_bf16)."""
+    from util import record_margin
+    fx = load(name)
+    in_ch = int(fx["meta/in_ch"])
+    np_sd, running = make_state(in_ch, int(fx["meta/seed_w"])), running_from(fx)
+    assert any(np.abs(v).max() > 0 for k, v in running.items() if k.endswith("running_mean"))
+    m = build(device, in_ch, 0.2, np_sd, running).eval().set_compute_dtype(dtype)
+    with torch.no_grad():
+        out = m(torch.from_numpy(fx["x"]).to(device)).cpu().numpy()
+    assert out.shape == fx["out"].shape and out.dtype == np.float32
+    o32 = _oracle_eval(np_sd, running, fx["x"], None)
+    o16 = _oracle_eval(np_sd, running, fx["x"], dtype)
+    assert np.abs(o32 - fx["out"]).max() <= OUT_ABS
+    ref_err = float(np.abs(o16 - o32).max())
+    our_err = float(np.abs(out - fx["out"]).max())
+    tag = "bf16" if dtype == torch.bfloat16 else "f16"
+    print(f"{name} {tag} eval: out max-abs ours {our_err:.2e} ref-autocast {ref_err:.2e}")
+    record_margin(f"eval_calibrated_{tag}_{name}", out_max_abs=our_err, ref_autocast=ref_err,
+                  out_bound=1.5 * ref_err, err_over_bound=our_err / (1.5 * ref_err))
+    assert our_err <= 1.5 * ref_err
+
+
+@pytest.mark.parametrize("name", EVAL_FIXTURES)
+def test_eval_fused_matches_unfused(device, name, monkeypatch):
+    """fp32 eval with the BN + LeakyReLU (+ skip) in the conv epilogues
+    (EVAL_FUSED, the default) and with separate BN-apply passes: each within
+    OUT_ABS of the fixture, and of each other."""
+    from nsm_amd import unet
+    from util import record_margin
+    fx = load(name)
+    in_ch = int(fx["meta/in_ch"])
+    outs = {}
+    for fused in (False, True):
+        with monkeypatch.context() as mp:
+            mp.setattr(unet, "EVAL_FUSED", fused)
+            m = build(device, in_ch, 0.2, make_state(in_ch, int(fx["meta/seed_w"])),
+                      running_from(fx)).eval()
+            with torch.no_grad():
+                outs[fused] = m(torch.from_numpy(fx["x"]).to(device)).cpu().numpy()
+    errs = {f: float(np.abs(o - fx["out"]).max()) for f, o in outs.items()}
+    both = float(np.abs(outs[True] - outs[False]).max())
+    print(f"{name}: fused {errs[True]:.2e} unfused {errs[False]:.2e} fused-unfused {both:.2e}")
+    record_margin(f"eval_fused_vs_unfused_{name}", fused=errs[True], unfused=errs[False],
+                  between=both, bound=OUT_ABS)
+    assert errs[True] <= OUT_ABS and errs[False] <= OUT_ABS
+    assert both <= OUT_ABS
