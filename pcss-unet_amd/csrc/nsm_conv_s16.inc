@@ -899,6 +899,10 @@ static WgradPlan plan_wgrad_b(int B, int H, int W, int cin_p, int cout_p, int ks
     return pl;
   }
   WgradPlan pl = plan_wgrad(B, H, W, cin_p, cout_p, ksize);
+  // an N tile covers whole taps or divides one (s16_conv_wgrad checks it): the
+  // channel counts that fit the planned tile neither way (96: 128 columns of a
+  // 3x3, 64 of a 1x1) take 32-column tiles
+  if (cin_p % pl.BN != 0 && pl.BN % cin_p != 0 && cin_p % 32 == 0) pl.BN = 32;
   const long long K = (long long)B * H * W;
   long long kc = (pl.kchunk + BKB - 1) / BKB * BKB;
   long long sp = (K + kc - 1) / kc;
