@@ -676,7 +676,30 @@ int nsm_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr, floa
  *   momentum buffer is set to the gradient on the first step taken (step[0]
  *   == 1, so a skipped first step leaves the next one to initialise it) and is
  *   momentum*buf + g afterwards; momentum == 0 touches no buffer (buf may be
- *   NULL). */
+ *   NULL).
+ * nsm_grad_tail_scaled: nsm_grad_tail with a dynamic loss scale kept on the
+ *   device. scaler_state holds NSM_SCALER_WORDS 32-bit words: [0] the scale
+ *   (fp32), [1] the growth tracker (int32), [2] found_inf of the last call,
+ *   [3] overflow steps so far, [4] growths so far, [5..7] reserved (zero). The
+ *   scale is read from scaler_state[0] (the value the backward of this step was
+ *   seeded with, by stream order) where nsm_grad_tail takes `scale`, with the
+ *   same arithmetic: at an equal scale seg_coef, stat and flags are bitwise
+ *   those of nsm_grad_tail. found_inf = the census saw a NaN or Inf in the
+ *   rank-averaged scaled gradient, or flags[3]. on_overflow 0 (repair): the
+ *   tail's decisions are unchanged; 1 (skip): found_inf also sets flags[0], so
+ *   the update kernels return and step[0] does not advance. Then
+ *   torch.amp.GradScaler's rule (torch._amp_update_scale_), in the same launch:
+ *     found_inf: scale *= backoff_factor, tracker = 0;
+ *     else, if the step is taken: tracker += 1, and when it reaches
+ *       growth_interval: tracker = 0 and scale *= growth_factor unless the
+ *       product is not finite;
+ *     else (skipped for `huge` or `postclip`): unchanged.
+ *   Needs growth_factor > 1, 0 < backoff_factor < 1, growth_interval > 0.
+ *   Same launch count as nsm_grad_tail; no host sync, no atomics.
+ * nsm_scaler_set: scaler_state[0] = scale (finite, > 0), [1] = tracker (>= 0);
+ *   the other words keep their values (zero the buffer once before the first
+ *   call). */
+#define NSM_SCALER_WORDS 8
 int64_t nsm_tail_chunk(void);
 int nsm_tail_plan(const int64_t* seg_off, int nseg, int* blk_seg, int64_t* blk_lo,
                   int64_t* blk_hi, int* seg_blk, int cap);
@@ -686,6 +709,14 @@ int nsm_grad_tail(float* g, int nseg, const int64_t* seg_off, const int* seg_blk
                   float inv_world, float scale, float max_norm, const float* noise, uint64_t seed,
                   void* ws, size_t ws_bytes, float* seg_coef, float* stat, int* flags, int* step,
                   void* stream);
+int nsm_grad_tail_scaled(float* g, int nseg, const int64_t* seg_off, const int* seg_blk,
+                         const int* blk_seg, const int64_t* blk_lo, const int64_t* blk_hi,
+                         int nblk, float inv_world, void* scaler_state, float max_norm,
+                         const float* noise, uint64_t seed, void* ws, size_t ws_bytes,
+                         float* seg_coef, float* stat, int* flags, int* step, float growth_factor,
+                         float backoff_factor, int growth_interval, int on_overflow,
+                         void* stream);
+int nsm_scaler_set(void* scaler_state, float scale, int tracker, void* stream);
 int nsm_adamw_tail(float* p, const float* g, float* m, float* v, const int* blk_seg,
                    const int64_t* blk_lo, const int64_t* blk_hi, int nblk, const float* seg_coef,
                    const int* flags, const int* step, double lr, double beta1, double beta2,

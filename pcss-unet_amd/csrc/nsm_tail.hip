@@ -286,10 +286,40 @@ __global__ void __launch_bounds__(TAIL_THREADS) tail_repair_kernel(
 // zero}; stat = {total norm, clip coef, max_norm, max post-clip norm};
 // flags = {skip, repaired, severe, nonfinite, huge (>1e5), postclip (>10),
 // n rescaled, n zeroed}; step[0] += !skip.
+//
+// DYN = false is the static loss scale (the kernel argument `scale`). DYN = true
+// (nsm_grad_tail_scaled) reads the scale from the scaler state sc.state[0], the
+// value the loss backward of this step was seeded with, and, once the flags are
+// known, thread 0 applies torch.amp.GradScaler's update rule to the state
+// (torch._amp_update_scale_). found_inf = the census saw a NaN or Inf in the
+// (rank-averaged) scaled gradient, or a non-finite norm survived (flags[3]); with
+// on_overflow == 1 it also skips the step. A step skipped for another reason
+// (huge, postclip: the reference `continue`s before scaler.update()) leaves the
+// scale and the tracker alone. Everything before the update is the same
+// arithmetic in both instantiations, so at an equal scale seg_coef, stat and
+// flags are bitwise equal (tests/test_gpu_loss_scale.py).
+struct TailScaler {
+  int* state;  // NSM_SCALER_WORDS words: scale (fp32 bits), tracker, found_inf, overflows, growths
+  float growth, backoff;
+  int interval, on_overflow;
+};
+
+template <bool DYN>
 __global__ void __launch_bounds__(1024) tail_finalize_kernel(
-    const int* __restrict__ seg_blk, int nseg, float scale, float max_norm, TailWs w,
-    float* __restrict__ seg_coef, float* __restrict__ stat, int* __restrict__ flags,
+    const int* __restrict__ seg_blk, int nseg, float scale, TailScaler sc, float max_norm,
+    TailWs w, float* __restrict__ seg_coef, float* __restrict__ stat, int* __restrict__ flags,
     int* __restrict__ step) {
+  // the pre-update scale, the same word in every thread (only thread 0 writes
+  // the state, after the block's last barrier). The words the update rewrites
+  // are read here too, so their latency hides behind the per-segment work
+  // instead of adding three dependent loads after the flags are known.
+  int tracker0 = 0, overflows0 = 0, growths0 = 0;
+  if (DYN) {
+    scale = __int_as_float(sc.state[0]);
+    tracker0 = sc.state[1];
+    overflows0 = sc.state[3];
+    growths0 = sc.state[4];
+  }
   __shared__ double sh_tot[16];
   __shared__ float sh_mx[16];
   __shared__ int sh_f[16][4];
@@ -402,7 +432,33 @@ __global__ void __launch_bounds__(1024) tail_finalize_kernel(
     stat[3] = M;
     const int severe = w.ctl[1];
     const int postclip = M > 10.f ? 1 : 0;  // main.py:408-418
-    const int skip = (severe || nonfin_t || huge_t || postclip) ? 1 : 0;
+    int skip = (severe || nonfin_t || huge_t || postclip) ? 1 : 0;
+    if (DYN) {
+      const int found_inf = (repaired || severe || nonfin_t) ? 1 : 0;
+      int tracker = tracker0, grew = 0;
+      if (found_inf) {
+        scale = scale * sc.backoff;
+        tracker = 0;
+      } else if (!skip) {
+        const int n = tracker + 1;
+        if (n == sc.interval) {
+          const float s2 = scale * sc.growth;
+          if (is_finite_f(s2)) {  // false for NaN too
+            scale = s2;
+            grew = 1;
+          }
+          tracker = 0;
+        } else {
+          tracker = n;
+        }
+      }
+      if (found_inf && sc.on_overflow) skip = 1;
+      sc.state[0] = __float_as_int(scale);
+      sc.state[1] = tracker;
+      sc.state[2] = found_inf;
+      sc.state[3] = overflows0 + found_inf;
+      sc.state[4] = growths0 + grew;
+    }
     flags[0] = skip;
     flags[1] = repaired ? 1 : 0;
     flags[2] = severe;
@@ -553,13 +609,14 @@ extern "C" size_t nsm_tail_ws_bytes(int nseg, int nblk) {
   return tail_ws_layout(nseg, nblk, nullptr, nullptr);
 }
 
-extern "C" int nsm_grad_tail(float* g, int nseg, const int64_t* seg_off, const int* seg_blk,
-                             const int* blk_seg, const int64_t* blk_lo, const int64_t* blk_hi,
-                             int nblk, float inv_world, float scale, float max_norm,
-                             const float* noise, uint64_t seed, void* ws, size_t ws_bytes,
-                             float* seg_coef, float* stat, int* flags, int* step, void* stream) {
+// the launch sequence of both entries: sc.state == NULL is the static scale
+static int grad_tail_launch(float* g, int nseg, const int64_t* seg_off, const int* seg_blk,
+                            const int* blk_seg, const int64_t* blk_lo, const int64_t* blk_hi,
+                            int nblk, float inv_world, float scale, TailScaler sc, float max_norm,
+                            const float* noise, uint64_t seed, void* ws, size_t ws_bytes,
+                            float* seg_coef, float* stat, int* flags, int* step, void* stream) {
   NSM_CHECK_ARG(g && seg_off && seg_blk && blk_seg && blk_lo && blk_hi && ws && seg_coef && stat &&
-                    flags && step && nseg > 0 && nblk > 0 && scale > 0.f,
+                    flags && step && nseg > 0 && nblk > 0,
                 "grad_tail: bad args");
   NSM_CHECK_ARG(ws_bytes >= nsm_tail_ws_bytes(nseg, nblk), "grad_tail: workspace too small");
   TailWs w;
@@ -573,9 +630,60 @@ extern "C" int nsm_grad_tail(float* g, int nseg, const int64_t* seg_off, const i
   hipLaunchKernelGGL(tail_repair_kernel, dim3(nblk), dim3(TAIL_THREADS), 0, s, g, blk_seg, blk_lo,
                      blk_hi, noise, seed, step, w);
   NSM_LAUNCH_CHECK("tail_repair");
-  hipLaunchKernelGGL(tail_finalize_kernel, dim3(1), dim3(1024), 0, s, seg_blk, nseg, scale,
-                     max_norm, w, seg_coef, stat, flags, step);
+  if (sc.state)
+    hipLaunchKernelGGL(tail_finalize_kernel<true>, dim3(1), dim3(1024), 0, s, seg_blk, nseg, scale,
+                       sc, max_norm, w, seg_coef, stat, flags, step);
+  else
+    hipLaunchKernelGGL(tail_finalize_kernel<false>, dim3(1), dim3(1024), 0, s, seg_blk, nseg,
+                       scale, sc, max_norm, w, seg_coef, stat, flags, step);
   NSM_LAUNCH_CHECK("tail_finalize");
+  return 0;
+}
+
+extern "C" int nsm_grad_tail(float* g, int nseg, const int64_t* seg_off, const int* seg_blk,
+                             const int* blk_seg, const int64_t* blk_lo, const int64_t* blk_hi,
+                             int nblk, float inv_world, float scale, float max_norm,
+                             const float* noise, uint64_t seed, void* ws, size_t ws_bytes,
+                             float* seg_coef, float* stat, int* flags, int* step, void* stream) {
+  NSM_CHECK_ARG(scale > 0.f, "grad_tail: bad args");
+  return grad_tail_launch(g, nseg, seg_off, seg_blk, blk_seg, blk_lo, blk_hi, nblk, inv_world,
+                          scale, TailScaler{nullptr, 1.f, 1.f, 0, 0}, max_norm, noise, seed, ws,
+                          ws_bytes, seg_coef, stat, flags, step, stream);
+}
+
+extern "C" int nsm_grad_tail_scaled(float* g, int nseg, const int64_t* seg_off, const int* seg_blk,
+                                    const int* blk_seg, const int64_t* blk_lo,
+                                    const int64_t* blk_hi, int nblk, float inv_world,
+                                    void* scaler_state, float max_norm, const float* noise,
+                                    uint64_t seed, void* ws, size_t ws_bytes, float* seg_coef,
+                                    float* stat, int* flags, int* step, float growth_factor,
+                                    float backoff_factor, int growth_interval, int on_overflow,
+                                    void* stream) {
+  NSM_CHECK_ARG(scaler_state && growth_factor > 1.f && backoff_factor > 0.f &&
+                    backoff_factor < 1.f && growth_interval > 0 &&
+                    (on_overflow == 0 || on_overflow == 1),
+                "grad_tail_scaled: bad scaler args");
+  return grad_tail_launch(g, nseg, seg_off, seg_blk, blk_seg, blk_lo, blk_hi, nblk, inv_world, 0.f,
+                          TailScaler{(int*)scaler_state, growth_factor, backoff_factor,
+                                     growth_interval, on_overflow},
+                          max_norm, noise, seed, ws, ws_bytes, seg_coef, stat, flags, step, stream);
+}
+
+// scaler state <- {scale, tracker}; the other words (found_inf, the two
+// counters, the reserved ones) keep their values. One thread, plain stores.
+__global__ void scaler_set_kernel(int* state, float scale, int tracker) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    state[0] = __float_as_int(scale);
+    state[1] = tracker;
+  }
+}
+
+extern "C" int nsm_scaler_set(void* scaler_state, float scale, int tracker, void* stream) {
+  NSM_CHECK_ARG(scaler_state && scale > 0.f && scale <= FLT_MAX && tracker >= 0,
+                "scaler_set: bad args");
+  hipLaunchKernelGGL(scaler_set_kernel, dim3(1), dim3(64), 0, as_stream(stream),
+                     (int*)scaler_state, scale, tracker);
+  NSM_LAUNCH_CHECK("scaler_set");
   return 0;
 }
 

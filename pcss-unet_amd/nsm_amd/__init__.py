@@ -11,6 +11,7 @@ from .losses import (CustomLoss, EnhancedCustomLoss, L1Loss, PerturbationLoss,  
                      ssim_loss)
 from .optim import (FlatAdam, FlatAdamW, FlatSGD, allreduce_grads, flat_grad,  # noqa: F401
                     make_optimizer)
+from .grad_scaler import GradScaler  # noqa: F401
 from .infer import GraphedUnet  # noqa: F401
 from .step import GraphedTrainStep  # noqa: F401
 from .vgg import MultiLayerVGGLoss  # noqa: F401

@@ -161,6 +161,9 @@ _SIGS = {
     "nsm_tail_plan": (I, [P, I, P, P, P, P, I]),
     "nsm_tail_ws_bytes": (Z, [I, I]),
     "nsm_grad_tail": (I, [P, I, P, P, P, P, P, I, F, F, F, P, U64, P, Z, P, P, P, P, P]),
+    "nsm_grad_tail_scaled": (I, [P, I, P, P, P, P, P, I, F, P, F, P, U64, P, Z, P, P, P, P, F, F,
+                                 I, I, P]),
+    "nsm_scaler_set": (I, [P, F, I, P]),
     "nsm_adamw_tail": (I, [P, P, P, P, P, P, P, I, P, P, P, D, D, D, D, D, P]),
     "nsm_adam_tail": (I, [P, P, P, P, P, P, P, I, P, P, P, D, D, D, D, D, P]),
     "nsm_sgd_tail": (I, [P, P, P, P, P, P, I, P, P, P, D, D, D, P]),

@@ -32,6 +32,12 @@ and the same device tail: everything up to the update (`nsm_grad_tail`) is
 shared, only the last kernel differs (`nsm_adam_tail` / `nsm_sgd_tail`), and
 their checkpoints are torch.optim.Adam's / torch.optim.SGD's.
 `make_optimizer(params, optimizer_type, lr)` is that three-way block.
+
+The loss scale of the fp16 mode is either a constant (`grad_scale=`, a kernel
+argument of `nsm_grad_tail`) or an `nsm_amd.GradScaler` (`grad_scaler=`): then
+the tail is `nsm_grad_tail_scaled`, which reads the scale from the scaler's
+device state and applies torch.amp.GradScaler's update rule to it in the same
+finalize kernel (grad_scaler.py).
 """
 import math
 import os
@@ -158,8 +164,15 @@ class _FlatOptimizer(torch.optim.Optimizer):
     _REFUSED = {}
 
     def __init__(self, params, defaults, max_grad_norm=None, world_size=1, sanitize=False,
-                 grad_scale=1.0, seed=None):
+                 grad_scale=1.0, seed=None, grad_scaler=None):
         params = list(params)
+        if grad_scaler is not None:
+            if float(grad_scale) != 1.0:
+                raise ValueError(f"{type(self).__name__}: grad_scale is the static loss scale; "
+                                 "with grad_scaler= the scale is the scaler's")
+            if grad_scaler.is_enabled() and not sanitize:
+                raise ValueError(f"{type(self).__name__}: grad_scaler needs sanitize=True (the "
+                                 "device tail is what unscales and updates the scale)")
         super().__init__(params, defaults)
         if len(self.param_groups) != 1:
             raise ValueError(f"{type(self).__name__} supports one param group")
@@ -182,6 +195,11 @@ class _FlatOptimizer(torch.optim.Optimizer):
         self.inv_world = 1.0 / world_size
         self.sanitize = sanitize
         self.grad_scale = float(grad_scale)
+        # nsm_amd.GradScaler: the loss scale is device state the tail reads and
+        # updates (a disabled one is kept for scaler.step(), and changes nothing)
+        self.grad_scaler = grad_scaler
+        self._scaler = grad_scaler if grad_scaler is not None and grad_scaler.is_enabled() \
+            else None
         self.step_count = 0          # host count (sanitize=False: no step is ever skipped)
         nb = lib.nsm_loss_blocks(total)
         self._partial = torch.empty(nb, dtype=torch.float32, device=dev)
@@ -250,8 +268,12 @@ class _FlatOptimizer(torch.optim.Optimizer):
     # ---- what GraphedTrainStep needs -----------------------------------------
     def step_state(self):
         """Every tensor a step writes besides its scratch: the flat parameters,
-        the optimizer's flat state, the tail's device counters and flags."""
-        return [self.flat] + self._moments() + [self._step_dev, self.flags, self.stat]
+        the optimizer's flat state, the tail's device counters and flags (and
+        the grad scaler's device state)."""
+        st = [self.flat] + self._moments() + [self._step_dev, self.flags, self.stat]
+        if self._scaler is not None:
+            st.append(self._scaler.state_tensor())
+        return st
 
     def step_hyper(self):
         """The hyper-parameters a step passes as kernel arguments (a captured
@@ -259,6 +281,9 @@ class _FlatOptimizer(torch.optim.Optimizer):
         g = self.param_groups[0]
         vals = tuple(tuple(g[k]) if isinstance(g[k], (tuple, list)) else float(g[k])
                      for k in self._hyper_keys())
+        if self._scaler is not None:
+            # the scale itself is device state: its changes need no new capture
+            return vals + (self.max_grad_norm, self._scaler.tail_args())
         return vals + (self.max_grad_norm, self.grad_scale)
 
     # main.py:357-358
@@ -281,11 +306,19 @@ class _FlatOptimizer(torch.optim.Optimizer):
         st = stream()
         if self.sanitize:
             mx = float(self.max_grad_norm) if self.max_grad_norm is not None else float("inf")
-            call("nsm_grad_tail", ptr(g), self._nseg, ptr(self._seg_off), ptr(self._seg_blk),
-                 ptr(self._blk_seg), ptr(self._blk_lo), ptr(self._blk_hi), self._nblk,
-                 self.inv_world, self.grad_scale, mx, ptr(noise), self.seed, ptr(self._ws),
-                 self._ws.numel(), ptr(self._seg_coef), ptr(self.stat), ptr(self.flags),
-                 ptr(self._step_dev), st)
+            if self._scaler is not None:
+                call("nsm_grad_tail_scaled", ptr(g), self._nseg, ptr(self._seg_off),
+                     ptr(self._seg_blk), ptr(self._blk_seg), ptr(self._blk_lo), ptr(self._blk_hi),
+                     self._nblk, self.inv_world, ptr(self._scaler.state_tensor()), mx, ptr(noise),
+                     self.seed, ptr(self._ws), self._ws.numel(), ptr(self._seg_coef),
+                     ptr(self.stat), ptr(self.flags), ptr(self._step_dev),
+                     *self._scaler.tail_args(), st)
+            else:
+                call("nsm_grad_tail", ptr(g), self._nseg, ptr(self._seg_off), ptr(self._seg_blk),
+                     ptr(self._blk_seg), ptr(self._blk_lo), ptr(self._blk_hi), self._nblk,
+                     self.inv_world, self.grad_scale, mx, ptr(noise), self.seed, ptr(self._ws),
+                     self._ws.numel(), ptr(self._seg_coef), ptr(self.stat), ptr(self.flags),
+                     ptr(self._step_dev), st)
             self._tail_update(g, grp, st)
             _bump(params)
             return None
@@ -421,9 +454,10 @@ class FlatAdamW(_FlatAdamFamily):
     _TAIL, _STEP = "nsm_adamw_tail", "nsm_adamw_step"
 
     def __init__(self, params, lr=7e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-3,
-                 max_grad_norm=None, world_size=1, sanitize=False, grad_scale=1.0, seed=None):
+                 max_grad_norm=None, world_size=1, sanitize=False, grad_scale=1.0, seed=None,
+                 grad_scaler=None):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay),
-                         max_grad_norm, world_size, sanitize, grad_scale, seed)
+                         max_grad_norm, world_size, sanitize, grad_scale, seed, grad_scaler)
 
 
 class FlatAdam(_FlatAdamFamily):
@@ -435,10 +469,10 @@ class FlatAdam(_FlatAdamFamily):
 
     def __init__(self, params, lr=7e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-4,
                  max_grad_norm=None, world_size=1, sanitize=False, grad_scale=1.0, seed=None,
-                 amsgrad=False, maximize=False):
+                 amsgrad=False, maximize=False, grad_scaler=None):
         self._check_refused(dict(amsgrad=amsgrad, maximize=maximize))
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay),
-                         max_grad_norm, world_size, sanitize, grad_scale, seed)
+                         max_grad_norm, world_size, sanitize, grad_scale, seed, grad_scaler)
 
 
 class FlatSGD(_FlatOptimizer):
@@ -458,12 +492,12 @@ class FlatSGD(_FlatOptimizer):
 
     def __init__(self, params, lr=7e-4, momentum=0.9, weight_decay=1e-4, max_grad_norm=None,
                  world_size=1, sanitize=False, grad_scale=1.0, seed=None, dampening=0,
-                 nesterov=False, maximize=False):
+                 nesterov=False, maximize=False, grad_scaler=None):
         self._check_refused(dict(dampening=dampening, nesterov=nesterov, maximize=maximize))
         if momentum < 0:
             raise ValueError(f"FlatSGD: invalid momentum {momentum}")
         super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay),
-                         max_grad_norm, world_size, sanitize, grad_scale, seed)
+                         max_grad_norm, world_size, sanitize, grad_scale, seed, grad_scaler)
 
     def _alloc_state(self):
         mu = self.param_groups[0]["momentum"]
@@ -540,7 +574,7 @@ def make_optimizer(params, optimizer_type, lr, **kw):
     AdamW(weight_decay=1e-3), anything else -> SGD(momentum=0.9,
     weight_decay=1e-4), on the flat-buffer optimizers. The comparison is the
     reference's (exact, case-sensitive); `kw` takes max_grad_norm, world_size,
-    sanitize, grad_scale and seed."""
+    sanitize, grad_scale, seed and grad_scaler."""
     if optimizer_type == 'adam':
         return FlatAdam(params, lr=lr, weight_decay=1e-4, **kw)
     elif optimizer_type == 'adamw':

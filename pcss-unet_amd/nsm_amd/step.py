@@ -19,8 +19,11 @@ What the graph holds fixed, and how the step stays the reference's:
   * version counters: each replay bumps those of the parameters and buffers
     (the kernels rewrote them), so infer.GraphedUnet refreshes its layouts;
   * hyper-parameters passed as kernel arguments (lr, betas or momentum, eps,
-    weight decay, max_norm, the loss scale): the step re-captures when one of
-    them changes (an epoch's LambdaLR / max_norm schedule costs one capture);
+    weight decay, max_norm, the static loss scale): the step re-captures when
+    one of them changes (an epoch's LambdaLR / max_norm schedule costs one
+    capture); a `nsm_amd.GradScaler`'s scale is device state instead, read by
+    the backward's seed and the tail and updated by the tail inside the graph,
+    so it moves without a capture;
   * parameter / buffer addresses: FlatAdamW's flat storage keeps them; a
     re-allocation raises.
 The constructor runs `warmup` eager steps on (x, y) to settle the caches,
@@ -38,7 +41,7 @@ from .optim import _bump, allreduce_grads
 
 class GraphedTrainStep:
     def __init__(self, model, loss_fn, optimizer, x, y, loss_scale=1.0, warmup=3,
-                 range_check_every=0):
+                 range_check_every=0, grad_scaler=None):
         require_gpu(x, "GraphedTrainStep input")
         # data parallel (Unet.data_parallel): the rank-0 BN broadcast, the
         # bucketed gradient all-reduce the backward issues and the wait for it
@@ -54,6 +57,20 @@ class GraphedTrainStep:
                              "count on the device")
         self.model, self.loss_fn, self.opt = model, loss_fn, optimizer
         self.loss_scale = float(loss_scale)
+        # nsm_amd.GradScaler (default: the optimizer's): the backward is seeded
+        # from the scaler's own scale word, which the captured tail updates, so
+        # the scale moves from replay to replay with no new capture
+        if grad_scaler is None:
+            grad_scaler = getattr(optimizer, "grad_scaler", None)
+        if grad_scaler is not None and getattr(optimizer, "grad_scaler", None) is not grad_scaler:
+            raise ValueError("GraphedTrainStep: grad_scaler must be the one the optimizer was "
+                             "built with (its tail unscales by it)")
+        if grad_scaler is not None and self.loss_scale != 1.0:
+            raise ValueError("GraphedTrainStep: loss_scale is the static loss scale; with a "
+                             "grad_scaler the scale is the scaler's")
+        self.grad_scaler = grad_scaler
+        self._scaler = grad_scaler if grad_scaler is not None and grad_scaler.is_enabled() \
+            else None
         self.x = x.detach().clone().requires_grad_(x.requires_grad)
         self.y = y.detach().clone()
         self.warmup = warmup
@@ -66,6 +83,8 @@ class GraphedTrainStep:
         self._capture()
 
     def _hyper(self):
+        if self._scaler is not None:
+            return self.opt.step_hyper()
         return self.opt.step_hyper() + (self.loss_scale,)
 
     def _addresses(self):
@@ -94,7 +113,13 @@ class GraphedTrainStep:
 
     def _capture(self, warmup=None):
         warmup = self.warmup if warmup is None else warmup
-        self._seed = torch.full((), self.loss_scale, dtype=torch.float32, device=self.x.device)
+        if self._scaler is not None:
+            # the scale word itself (opt.step_state() holds the scaler's state, so
+            # the warm-up steps' backoffs and growths are undone below)
+            self._seed = self._scaler.seed
+        else:
+            self._seed = torch.full((), self.loss_scale, dtype=torch.float32,
+                                    device=self.x.device)
         side = torch.cuda.Stream(device=self.x.device)
         side.wait_stream(torch.cuda.current_stream())
         saved = [t.detach().clone() for t in self._state()]
