@@ -621,6 +621,46 @@ int nsm_ssim_fwd(const float* o, const float* t, int B, int H, int W, float data
                  const float* base, float* partial, float* coef, float* out, void* stream);
 int nsm_ssim_bwd(const float* o, const float* t, const float* coef, int B, int H, int W, float w,
                  const float* gscale, float* grad, int accumulate, void* stream);
+/* measure_temporal_instability with motion vectors (pert_loss.py:170-199 takes
+ * `motion_vectors` and leaves their branch as `pass`, so it raises there; this
+ * is the paper's Eq. 3): D_t(p) = |I_t(p) - I_{t-1}(m(p))|,
+ * E = mean(exp(alpha D) - 1). Planar NCHW fp32; cur, prev [B,C,H,W]; mv
+ * [B,2,H,W] in pixels, channel 0 along the width:
+ *   m(p) = (x + mv[b,0,y,x] * scale_x, y + mv[b,1,y,x] * scale_y),
+ * integer coordinates are pixel centres (align_corners=True), bilinear taps from
+ * floor with the cell clamped so that W-1 and H-1 are valid positions. A pixel
+ * is rejected (all its C elements) when m(p) is not finite or lies outside
+ * [0, W-1] x [0, H-1] (inclusive; tested in floating point, and a rejected
+ * pixel's taps are clamped into the image: nothing outside the buffers is read
+ * whatever mv holds); with depth_cur/depth_prev [B,1,H,W] when
+ * !(|z_t - z~| <= depth_tol * |z_t|); with normal_cur/normal_prev [B,3,H,W]
+ * when !(dot(n_t, n~) >= normal_cos). z~, n~: the previous frame's values
+ * interpolated with the same four weights (n~ is not renormalised). Each
+ * pointer pair may be NULL (test skipped); mv may be NULL (no motion; then
+ * depth and normals must be NULL too).
+ * nsm_temporal_blocks: blocks per image (0: unsupported shape, among them
+ *   C*H*W >= 2^31 and H or W above 2^24).
+ * nsm_temporal_pair: one frame pair, one launch. psum (float) and pcnt (int)
+ *   hold B * nsm_temporal_blocks words each, [B][blocks]: per block the fp32 sum
+ *   of exp(alpha D) - 1 over the surviving elements and their number. No atomics.
+ * nsm_temporal_finalize: psum, pcnt are the slabs of npairs pairs, [npairs][B][per].
+ *   One block, every sum in double in a fixed order: sums[npairs*B] (fp32) and
+ *   counts[npairs*B] (int64) per (pair, image); out[0] = the mean over the pairs
+ *   of (sum over the batch) / (all_count > 0 ? all_count : surviving count over
+ *   the batch), a pair whose divisor is 0 contributing 0; acc (may be NULL):
+ *   two device doubles, acc[0] += sum of the pair values, acc[1] += npairs.
+ * nsm_reproject: the same lookup as an op: out[b,c,y,x] = the bilinear sample of
+ *   prev at m(p) (0 where rejected), valid[b,y,x] = 1 where m(p) is inside. */
+int nsm_temporal_blocks(int B, int C, int H, int W);
+int nsm_temporal_pair(const float* cur, const float* prev, const float* mv, const float* depth_cur,
+                      const float* depth_prev, const float* normal_cur, const float* normal_prev,
+                      int B, int C, int H, int W, float scale_x, float scale_y, float alpha,
+                      float depth_tol, float normal_cos, float* psum, int* pcnt, void* stream);
+int nsm_temporal_finalize(const float* psum, const int* pcnt, int npairs, int B, int per,
+                          int64_t all_count, float* sums, int64_t* counts, float* out, double* acc,
+                          void* stream);
+int nsm_reproject(const float* prev, const float* mv, int B, int C, int H, int W, float scale_x,
+                  float scale_y, float* out, unsigned char* valid, void* stream);
 /* PerturbationLoss.perturb_input (pert_loss.py:26-59):
  * per-channel unbiased std over the batch of NCHW x -> std[C] */
 int nsm_channel_std(const float* x, int B, int C, int H, int W, float* partial, float* std,

@@ -1,0 +1,342 @@
+// The temporal-instability metric with motion-vector reprojection (the paper's
+// Eq. 3; pert_loss.py:170-199 takes `motion_vectors` and leaves their branch as
+// `pass`), and the reprojection as an op of its own. Planar NCHW fp32.
+//   D_t(p) = |I_t(p) - I_{t-1}(m(p))|,  E = mean(exp(alpha D) - 1)
+//   m(p) = (x + mv[b,0,y,x] * scale_x, y + mv[b,1,y,x] * scale_y) in pixels,
+//   integer coordinates are pixel centres (align_corners=True), bilinear.
+// A pixel is rejected when m(p) is not finite or leaves [0, W-1] x [0, H-1]
+// (tested in floating point, before any conversion to an integer; a rejected
+// pixel's taps are clamped into the image), and optionally when the previous
+// frame's interpolated depth or normal disagrees with the current one:
+//   !(|z_t - z~| <= depth_tol |z_t|)   or   !(dot(n_t, n~) >= normal_cos)
+// (n~ is not renormalised; a NaN on either side rejects).
+// One thread works on TP_VEC pixels of one image plane: the taps and the four
+// weights are computed once per pixel (reproject_taps, shared by both kernels)
+// and reused for every channel, the depth and the normals. The lanes of a wave
+// hold 64 consecutive pixels per slot, so a wave reads cur, mv, depth and
+// normals as whole 256-byte runs and its gathers from the previous frame land
+// on as few cache lines as the motion field allows (DESIGN.md has the measured
+// comparison with four consecutive pixels per thread and 16-byte loads, which
+// is 1.4 times slower: the gathers, 4 per plane and pixel, set the pace). The
+// gathers are unconditional (a rejected pixel's taps are in the image), so the
+// compiler issues them back to back. Surviving elements add exp(alpha D) - 1
+// to an fp32 block sum and 1 to an integer block count; both go to a slab
+// [B][blocks per image] per pair, and a single-block finalize sums the slabs
+// of all pairs in a fixed order in double. No atomics: bitwise reproducible.
+#include <math.h>
+#include "nsm_common.h"
+
+namespace nsm {
+
+constexpr int TP_THREADS = 256, TP_VEC = 4;
+constexpr int TP_PIX = TP_THREADS * TP_VEC;  // pixels of one block
+
+// the four taps of one pixel: plane offsets i00, i00 + dx, i00 + dy, i00 + dy + dx
+struct Taps {
+  int i00, dx, dy;
+  float w00, w01, w10, w11;
+  bool ok;
+};
+
+// Lookup position of pixel (x, y) under motion (mvx, mvy): the position test in
+// floating point, then the cell from floor, clamped so that px == W-1 is valid
+// (cell W-2, weight 1 on its right tap). A rejected pixel gets the cell (0, 0).
+__device__ __forceinline__ Taps reproject_taps(float mvx, float mvy, int x, int y, int H, int W,
+                                               float scale_x, float scale_y) {
+  Taps t;
+  const float px = fmaf(mvx, scale_x, (float)x), py = fmaf(mvy, scale_y, (float)y);
+  // NaN fails every comparison, +-Inf and 1e30 one of them
+  t.ok = px >= 0.f && px <= (float)(W - 1) && py >= 0.f && py <= (float)(H - 1);
+  const float cx = t.ok ? px : 0.f, cy = t.ok ? py : 0.f;
+  const int x0 = max(min((int)floorf(cx), W - 2), 0), y0 = max(min((int)floorf(cy), H - 2), 0);
+  const float fx = cx - (float)x0, fy = cy - (float)y0;
+  const float gx = 1.f - fx, gy = 1.f - fy;
+  t.i00 = y0 * W + x0;
+  t.dx = W > 1 ? 1 : 0;
+  t.dy = H > 1 ? W : 0;
+  t.w00 = gy * gx;
+  t.w01 = gy * fx;
+  t.w10 = fy * gx;
+  t.w11 = fy * fx;
+  return t;
+}
+
+__device__ __forceinline__ float tap_sample(const float* __restrict__ plane, const Taps& t) {
+  const float* p = plane + t.i00;
+  return (t.w00 * p[0] + t.w01 * p[t.dx]) + (t.w10 * p[t.dy] + t.w11 * p[t.dy + t.dx]);
+}
+
+// plane pixel of slot j (< TP_VEC) of this thread in block blk of its image:
+// a wave owns 64 * TP_VEC consecutive pixels, slot j of its lanes 64 consecutive
+// ones of them
+__device__ __forceinline__ uint32_t slot_pixel(uint32_t blk, int j) {
+  return blk * TP_PIX + (threadIdx.x & ~63u) * TP_VEC + j * 64 + (threadIdx.x & 63u);
+}
+
+// the thread's TP_VEC values of a plane of HW floats (0 past its end)
+__device__ __forceinline__ void ld_pix(const float* __restrict__ plane, uint32_t blk, uint32_t HW,
+                                       float (&v)[TP_VEC]) {
+#pragma unroll
+  for (int j = 0; j < TP_VEC; ++j) {
+    const uint32_t p = slot_pixel(blk, j);
+    v[j] = p < HW ? plane[p] : 0.f;
+  }
+}
+
+// the block's image b and block blk within it, and the taps of the thread's
+// TP_VEC pixels (ok = false past the plane's end). mv == NULL: no motion.
+__device__ __forceinline__ void thread_taps(const float* __restrict__ mv, int H, int W, FastDiv dw,
+                                            int per, float scale_x, float scale_y, int& b,
+                                            uint32_t& blk, Taps (&t)[TP_VEC]) {
+  const uint32_t HW = (uint32_t)H * W;
+  b = blockIdx.x / per;
+  blk = blockIdx.x - b * per;
+  float mx[TP_VEC] = {0.f, 0.f, 0.f, 0.f}, my[TP_VEC] = {0.f, 0.f, 0.f, 0.f};
+  if (mv) {
+    const float* m = mv + (size_t)b * 2 * HW;
+    ld_pix(m, blk, HW, mx);
+    ld_pix(m + HW, blk, HW, my);
+  }
+#pragma unroll
+  for (int j = 0; j < TP_VEC; ++j) {
+    const uint32_t p = slot_pixel(blk, j);
+    if (p < HW) {
+      const uint32_t y = fdiv(p, dw);
+      t[j] = reproject_taps(mx[j], my[j], (int)(p - y * W), (int)y, H, W, scale_x, scale_y);
+    } else {
+      t[j] = Taps{0, 0, 0, 0.f, 0.f, 0.f, 0.f, false};
+    }
+  }
+}
+
+// psum[blk], pcnt[blk]: the block's sum of exp(alpha D) - 1 over its surviving
+// elements and their number. zc/zp (depth of the current / previous frame,
+// [B,1,H,W]) and nc/np (normals, [B,3,H,W]) may be NULL in pairs.
+__global__ void __launch_bounds__(TP_THREADS)
+    temporal_pair_kernel(const float* __restrict__ cur, const float* __restrict__ prev,
+                         const float* __restrict__ mv, const float* __restrict__ zc,
+                         const float* __restrict__ zp, const float* __restrict__ nc,
+                         const float* __restrict__ np, int C, int H, int W, FastDiv dw, int per,
+                         float scale_x, float scale_y, float alpha, float depth_tol,
+                         float normal_cos, float* __restrict__ psum, int* __restrict__ pcnt) {
+  __shared__ float shs[TP_THREADS / 64];
+  __shared__ int shc[TP_THREADS / 64];
+  const uint32_t HW = (uint32_t)H * W;
+  int b;
+  uint32_t blk;
+  Taps t[TP_VEC];
+  thread_taps(mv, H, W, dw, per, scale_x, scale_y, b, blk, t);
+  float s = 0.f;
+  int cnt = 0;
+  float v[TP_VEC];
+  if (zc) {
+    ld_pix(zc + (size_t)b * HW, blk, HW, v);
+    const float* zprev = zp + (size_t)b * HW;
+#pragma unroll
+    for (int j = 0; j < TP_VEC; ++j)
+      t[j].ok = t[j].ok && fabsf(v[j] - tap_sample(zprev, t[j])) <= depth_tol * fabsf(v[j]);
+  }
+  if (nc) {
+    float dot[TP_VEC] = {0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < 3; ++k) {
+      ld_pix(nc + ((size_t)b * 3 + k) * HW, blk, HW, v);
+      const float* nprev = np + ((size_t)b * 3 + k) * HW;
+#pragma unroll
+      for (int j = 0; j < TP_VEC; ++j)
+        dot[j] = fmaf(v[j], tap_sample(nprev, t[j]), dot[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < TP_VEC; ++j)
+      t[j].ok = t[j].ok && dot[j] >= normal_cos;
+  }
+  for (int c = 0; c < C; ++c) {
+    const size_t plane = ((size_t)b * C + c) * HW;
+    ld_pix(cur + plane, blk, HW, v);
+#pragma unroll
+    for (int j = 0; j < TP_VEC; ++j)
+      s += t[j].ok ? expf(alpha * fabsf(v[j] - tap_sample(prev + plane, t[j]))) - 1.f : 0.f;
+  }
+#pragma unroll
+  for (int j = 0; j < TP_VEC; ++j) cnt += t[j].ok ? C : 0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    s += __shfl_xor(s, o, 64);
+    cnt += __shfl_xor(cnt, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    shs[threadIdx.x >> 6] = s;
+    shc[threadIdx.x >> 6] = cnt;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float r = 0.f;
+    int rc = 0;
+    for (int w = 0; w < TP_THREADS / 64; ++w) {
+      r += shs[w];
+      rc += shc[w];
+    }
+    psum[blockIdx.x] = r;
+    pcnt[blockIdx.x] = rc;
+  }
+}
+
+// One block over the slabs of npairs pairs ([npairs][B][per]), pair after pair,
+// image after image, every sum in double and in a fixed order:
+//   sums[p*B + b], counts[p*B + b]: image b of pair p;
+//   value of pair p = sum_b sums / (all_count > 0 ? all_count : sum_b counts),
+//   0 when that divisor is 0; out[0] = mean of the pair values;
+//   acc (may be NULL): acc[0] += sum of the pair values, acc[1] += npairs.
+__global__ void __launch_bounds__(TP_THREADS)
+    temporal_finalize_kernel(const float* __restrict__ psum, const int* __restrict__ pcnt,
+                             int npairs, int B, int per, long long all_count,
+                             float* __restrict__ sums, long long* __restrict__ counts,
+                             float* __restrict__ out, double* acc) {
+#pragma clang fp contract(off)
+  __shared__ double shs[TP_THREADS / 64];
+  __shared__ long long shc[TP_THREADS / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double total = 0.0;
+  for (int p = 0; p < npairs; ++p) {
+    double ps = 0.0;
+    long long pc = 0;
+    for (int b = 0; b < B; ++b) {
+      const size_t base = ((size_t)p * B + b) * per;
+      double s = 0.0;
+      long long c = 0;
+      for (int i = threadIdx.x; i < per; i += TP_THREADS) {
+        s += (double)psum[base + i];
+        c += pcnt[base + i];
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o, 64);
+        c += __shfl_xor(c, o, 64);
+      }
+      __syncthreads();  // the previous image's words have been read
+      if (lane == 0) {
+        shs[wave] = s;
+        shc[wave] = c;
+      }
+      __syncthreads();
+      s = 0.0;
+      c = 0;
+      for (int w = 0; w < TP_THREADS / 64; ++w) {
+        s += shs[w];
+        c += shc[w];
+      }
+      if (threadIdx.x == 0) {
+        sums[(size_t)p * B + b] = (float)s;
+        counts[(size_t)p * B + b] = c;
+      }
+      ps += s;
+      pc += c;
+    }
+    const double den = all_count > 0 ? (double)all_count : (double)pc;
+    total += den > 0.0 ? ps / den : 0.0;
+  }
+  if (threadIdx.x == 0) {
+    out[0] = (float)(total / (double)npairs);
+    if (acc) {
+      acc[0] += total;
+      acc[1] += (double)npairs;
+    }
+  }
+}
+
+// out[b,c,y,x] = the bilinear sample of prev at m(p) (0 where rejected),
+// valid[b,y,x] = 1 where m(p) lies inside the image
+__global__ void __launch_bounds__(TP_THREADS)
+    reproject_kernel(const float* __restrict__ prev, const float* __restrict__ mv, int C, int H,
+                     int W, FastDiv dw, int per, float scale_x, float scale_y,
+                     float* __restrict__ out, unsigned char* __restrict__ valid) {
+  const uint32_t HW = (uint32_t)H * W;
+  int b;
+  uint32_t blk;
+  Taps t[TP_VEC];
+  thread_taps(mv, H, W, dw, per, scale_x, scale_y, b, blk, t);
+  unsigned char* vb = valid + (size_t)b * HW;
+#pragma unroll
+  for (int j = 0; j < TP_VEC; ++j) {
+    const uint32_t p = slot_pixel(blk, j);
+    if (p < HW) vb[p] = t[j].ok ? 1 : 0;
+  }
+  for (int c = 0; c < C; ++c) {
+    const size_t plane = ((size_t)b * C + c) * HW;
+    float v[TP_VEC];
+#pragma unroll
+    for (int j = 0; j < TP_VEC; ++j) {
+      const float q = tap_sample(prev + plane, t[j]);
+      v[j] = t[j].ok ? q : 0.f;
+    }
+    float* o = out + plane;
+#pragma unroll
+    for (int j = 0; j < TP_VEC; ++j) {
+      const uint32_t p = slot_pixel(blk, j);
+      if (p < HW) o[p] = v[j];
+    }
+  }
+}
+
+// fp32 holds pixel coordinates exactly below 2^24; C*H*W < 2^31 keeps every
+// plane offset in an int and every block count in an int
+static bool temporal_shape_ok(int B, int C, int H, int W) {
+  if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || H > (1 << 24) || W > (1 << 24)) return false;
+  if ((long long)C * H * W >= (1ll << 31)) return false;
+  return (long long)B * ceil_div((long long)H * W, TP_PIX) < (1ll << 31);
+}
+
+}  // namespace nsm
+
+using namespace nsm;
+
+extern "C" int nsm_temporal_blocks(int B, int C, int H, int W) {
+  if (!temporal_shape_ok(B, C, H, W)) return 0;
+  return ceil_div((long long)H * W, TP_PIX);
+}
+
+extern "C" int nsm_temporal_pair(const float* cur, const float* prev, const float* mv,
+                                 const float* depth_cur, const float* depth_prev,
+                                 const float* normal_cur, const float* normal_prev, int B, int C,
+                                 int H, int W, float scale_x, float scale_y, float alpha,
+                                 float depth_tol, float normal_cos, float* psum, int* pcnt,
+                                 void* stream) {
+  NSM_CHECK_ARG(cur && prev && psum && pcnt, "temporal_pair: null pointer");
+  NSM_CHECK_ARG(!depth_cur == !depth_prev && !normal_cur == !normal_prev,
+                "temporal_pair: depth and normals come for both frames of the pair or for none");
+  NSM_CHECK_ARG(mv || (!depth_cur && !normal_cur),
+                "temporal_pair: depth or normal rejection without motion vectors");
+  NSM_CHECK_ARG(temporal_shape_ok(B, C, H, W), "temporal_pair: shape %d x %d x %d x %d", B, C, H, W);
+  const int per = nsm_temporal_blocks(B, C, H, W);
+  hipLaunchKernelGGL(temporal_pair_kernel, dim3(B * per), dim3(TP_THREADS), 0, as_stream(stream),
+                     cur, prev, mv, depth_cur, depth_prev, normal_cur, normal_prev, C, H, W,
+                     make_fastdiv((uint32_t)W), per, scale_x, scale_y, alpha, depth_tol, normal_cos,
+                     psum, pcnt);
+  NSM_LAUNCH_CHECK("temporal_pair");
+  return 0;
+}
+
+extern "C" int nsm_temporal_finalize(const float* psum, const int* pcnt, int npairs, int B, int per,
+                                     int64_t all_count, float* sums, int64_t* counts, float* out,
+                                     double* acc, void* stream) {
+  NSM_CHECK_ARG(psum && pcnt && sums && counts && out, "temporal_finalize: null pointer");
+  NSM_CHECK_ARG(npairs > 0 && B > 0 && per > 0 && all_count >= 0,
+                "temporal_finalize: %d pairs x %d images x %d blocks, all_count %lld", npairs, B,
+                per, (long long)all_count);
+  hipLaunchKernelGGL(temporal_finalize_kernel, dim3(1), dim3(TP_THREADS), 0, as_stream(stream),
+                     psum, pcnt, npairs, B, per, (long long)all_count, sums, (long long*)counts, out,
+                     acc);
+  NSM_LAUNCH_CHECK("temporal_finalize");
+  return 0;
+}
+
+extern "C" int nsm_reproject(const float* prev, const float* mv, int B, int C, int H, int W,
+                             float scale_x, float scale_y, float* out, unsigned char* valid,
+                             void* stream) {
+  NSM_CHECK_ARG(prev && mv && out && valid, "reproject: null pointer");
+  NSM_CHECK_ARG(temporal_shape_ok(B, C, H, W), "reproject: shape %d x %d x %d x %d", B, C, H, W);
+  const int per = nsm_temporal_blocks(B, C, H, W);
+  hipLaunchKernelGGL(reproject_kernel, dim3(B * per), dim3(TP_THREADS), 0, as_stream(stream), prev,
+                     mv, C, H, W, make_fastdiv((uint32_t)W), per, scale_x, scale_y, out, valid);
+  NSM_LAUNCH_CHECK("reproject");
+  return 0;
+}

@@ -9,6 +9,8 @@ from .unet import DoubleConv, Unet, reserve_side_stream  # noqa: F401
 from .losses import (CustomLoss, EnhancedCustomLoss, L1Loss, PerturbationLoss,  # noqa: F401
                      detail_loss, detail_terms, l1_loss, measure_temporal_instability, ssim,
                      ssim_loss)
+from .temporal import (TemporalInstability, reproject,  # noqa: F401
+                       temporal_instability_terms)
 from .optim import (FlatAdam, FlatAdamW, FlatSGD, allreduce_grads, flat_grad,  # noqa: F401
                     make_optimizer)
 from .grad_scaler import GradScaler  # noqa: F401

@@ -129,6 +129,10 @@ _SIGS = {
     "nsm_ssim_blocks": (I, [I, I, I]),
     "nsm_ssim_fwd": (I, [P, P, I, I, I, F, F, P, P, P, P, P]),
     "nsm_ssim_bwd": (I, [P, P, P, I, I, I, F, P, P, I, P]),
+    "nsm_temporal_blocks": (I, [I, I, I, I]),
+    "nsm_temporal_pair": (I, [P, P, P, P, P, P, P, I, I, I, I, F, F, F, F, F, P, P, P]),
+    "nsm_temporal_finalize": (I, [P, P, I, I, I, L, P, P, P, P, P]),
+    "nsm_reproject": (I, [P, P, I, I, I, I, F, F, P, P, P]),
     "nsm_channel_std": (I, [P, I, I, I, I, P, P, P]),
     "nsm_perturb": (I, [P, P, P, I, I, I, I, F, P, P]),
     "nsm_sumsq": (I, [P, L, P, P, P]),

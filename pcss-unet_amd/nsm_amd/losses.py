@@ -65,7 +65,12 @@
   term joins `total` and the dict gains 'ssim_loss' = 1 - ssim (device scalar).
 * `measure_temporal_instability(frames, motion_vectors=None, alpha=5.0)`:
   pert_loss.py:166-199, mean over consecutive frame pairs of
-  mean(exp(alpha*|f_t - f_{t-1}|) - 1) (`nsm_expdiff_mean`).
+  mean(exp(alpha*|f_t - f_{t-1}|) - 1) (`nsm_expdiff_mean`). With
+  `motion_vectors` each pixel is compared with its reprojected position in the
+  previous frame (the paper's Eq. 3; the reference's branch is a stub that
+  raises), with optional depth / normal rejection: nsm_amd/temporal.py, which
+  also has `temporal_instability_terms`, `reproject` and the streaming
+  `TemporalInstability`; all four are re-exported here.
 """
 import os
 import warnings
@@ -74,6 +79,8 @@ import torch
 import torch.nn as nn
 
 from ._lib import call, lib, ptr, require_gpu, stream
+from .temporal import (TemporalInstability, measure_temporal_instability,  # noqa: F401
+                       reproject, temporal_instability_terms)
 
 VGG19_FILE = "vgg19-dcbb9e9d.pth"   # torchvision IMAGENET1K_V1 (customLoss.py:20)
 _VGG_WARNED = []
@@ -655,22 +662,3 @@ class EnhancedCustomLoss(nn.Module):
             losses["perturbation_loss"] = torch.zeros((), device=l1.device)
         losses["total_loss"] = total
         return total, losses
-
-
-def measure_temporal_instability(frames, motion_vectors=None, alpha=5.0):
-    """frames: sequence of same-shape tensors on the GPU (e.g. [B,1,H,W] outputs)."""
-    if len(frames) < 2:
-        return torch.tensor(0.0)
-    # motion_vectors: the reference accepts them but does not use them (pert_loss.py:184-187)
-    dev = frames[0].device
-    require_gpu(frames[0], "temporal-instability frames")
-    n = frames[0].numel()
-    partial = torch.empty(lib.nsm_loss_blocks(n), dtype=torch.float32, device=dev)
-    total = torch.zeros((), dtype=torch.float32, device=dev)
-    for t in range(1, len(frames)):
-        a = frames[t].detach().contiguous().to(torch.float32)
-        b = frames[t - 1].detach().contiguous().to(torch.float32)
-        out = torch.empty((), dtype=torch.float32, device=dev)
-        call("nsm_expdiff_mean", ptr(a), ptr(b), n, float(alpha), ptr(partial), ptr(out), stream())
-        total = total + out
-    return total / (len(frames) - 1)
