@@ -244,8 +244,8 @@ int nsm_wino_output_bf16(const float* Mb, int B, int H, int W, int cout_p, int t
  * this pair in the Python path. */
 /* Both F(4x4) transforms of the bf16 output gradient dY from one read: V
  * (the input gradient's operand, as nsm_wino_input_f16 of dY) and dM (as
- * nsm_wino_dout_f16), scale source amax_dy for both. NSM_BF16_DUAL selects it
- * in the Python path. */
+ * nsm_wino_dout_f16), scale source amax_dy for both. The Python path takes
+ * it wherever the input gradient is needed. */
 int nsm_wino_dual_f16(const void* dy, int lddy, int B, int H, int W, int c_p, int tile, void* V,
                       void* dM, const uint32_t* amax_dy, void* stream);
 /* nsm_wino_dual_f16 of a dY that is never stored: dY = k1 dz + k2 (y - mean) +

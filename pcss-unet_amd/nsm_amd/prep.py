@@ -30,12 +30,11 @@ KIND_WINO_F16 = 6
 KIND_PACK_F16 = 7   # IEEE half pack (the fp16-autocast mode's direct convolutions)
 # NSM_H2=0: the fp32 training step keeps fp32 Winograd operands (the GEMMs
 # split them in-kernel, nsm_conv_split16.inc) instead of the pre-split h2
-# tensors their producers write (nsm_conv_h2.inc)
+# tensors their producers write (nsm_conv_h2.inc). The DoubleConv 1x1
+# convolutions and conv2's direct 3x3 go with them: h2 operands written by
+# their producers (csrc/nsm_conv_h2d.inc), or fp32 ones (register-path f16x2
+# split) under NSM_H2=0
 H2_WINO = os.environ.get("NSM_H2", "1") != "0"
-# NSM_H2_1X1=0: the DoubleConv 1x1 convolutions of the fp32 training step keep
-# fp32 operands (register-path f16x2 split) instead of h2 operands written by
-# their producers (csrc/nsm_conv_h2d.inc); on with the h2 Winograd operands
-H2_1X1 = os.environ.get("NSM_H2_1X1", "1") != "0"
 # NSM_BF16_WINO=0: the bf16 training step's 3x3 forward at >= NSM_BF16_WINO_MIN
 # input channels stays on the direct implicit GEMM instead of Winograd F(4x4)
 # on single-plane scaled f16 operands (ops.conv3x3_wino_f16). Measured (B=64
@@ -234,8 +233,7 @@ class StepWeights:
                 # Only the first block: its input is the one written as h2
                 # (ops.input_prep_h2); a later direct 3x3 (NSM_WINOGRAD=0 or a
                 # raised NSM_WINO_MIN) reads the fp32 output of the block before
-                h2_3x3 = h2 and training and H2_1X1 and k == first
-
+                h2_3x3 = h2 and training and k == first
                 wf16 = bf16_wino(cip, dtype, training)
                 if wf16:   # Winograd F(4x4) forward: single-plane f16 U (kind 6)
                     am = ops.amax_slot(self.amax, n_am)
@@ -264,7 +262,7 @@ class StepWeights:
                     else:
                         pb.t[("w1", mode)] = add(pk, (ci, ci, 9, cip, cip, mode), c0.weight,
                                                  cip * 9 * cip, dtype, amax=am)
-            h2_1x1 = h2 and training and H2_1X1
+            h2_1x1 = h2 and training
             for mode in modes:
                 am = None
                 if h2_1x1 and mode != ops.PACK_FWD:

@@ -38,53 +38,14 @@ SLOPE = 0.2
 # forces one tile everywhere.
 WINOGRAD_MIN_CHANNELS = (int(os.environ.get("NSM_WINO_MIN", "64"))
                          if os.environ.get("NSM_WINOGRAD", "1") != "0" else 1 << 30)
-# NSM_ACT_POOL=0: the encoder block output and its AvgPool2d as two passes
-# (bn_act, avgpool2) instead of one (ops.bn_act_pool)
-ACT_POOL = os.environ.get("NSM_ACT_POOL", "1") != "0"
 # NSM_LAZY_DECODER=1 (bf16): compute the decoder block outputs c5, merge6-8
 # inside the next block's upsample (ops.Lazy) instead of materialising them.
 # Off by default: B=64 bf16 A/B 1214 -> 1189 frames/s (the act-on-load upsample
 # reads Y2 and the residual at every bilinear tap; conv9 stage +0.9 ms).
 LAZY_DECODER = os.environ.get("NSM_LAZY_DECODER", "0") != "0"
-# NSM_DUAL_WINO=0: the Winograd dgrad and wgrad transform the output gradient
-# in two separate reads of it instead of one (nsm_wino_dual_input)
-DUAL_TRANSFORM = os.environ.get("NSM_DUAL_WINO", "1") != "0"
-# NSM_LAZY_DY1=1: the dual transform forms dY1 per element from dA1 and Y1
-# (nsm_wino_dual_input_bn) instead of reading the dY1 nsm_bn_bwd_apply stored.
-# Off: it saves the dY1 round trip but the F(6x6) kernel then issues 128
-# loads per thread (two tensors over the overlapping 8x8 patches) and became
-# issue-bound — conv7 apply 152 + dual 250 us -> fused 484 us, conv6 210 ->
-# 260 us (only conv3 gained, 56 -> 48 us).
-LAZY_DY1 = os.environ.get("NSM_LAZY_DY1", "0") != "0"
-# NSM_LAZY_DY1_H2=0: on h2 Winograd operands, store dY1 (a second GEMM pass,
-# or nsm_bn_bwd_apply) instead of forming it in the dual transform. There the
-# F(6x6) BN-fused transform reads a block's pixel region once into LDS
-# (wino_dual_bn_lds_kernel), which removes the issue bound above.
-LAZY_DY1_H2 = os.environ.get("NSM_LAZY_DY1_H2", "1") != "0"
-# NSM_WGRAD_F16=0: the bf16 path's F(4x4) layers take their weight gradient
-# from the direct implicit GEMM instead of the Winograd domain (dM x V)
-WGRAD_F16 = os.environ.get("NSM_WGRAD_F16", "1") != "0"
-# NSM_BF16_DUAL=0: with WGRAD_F16, the bf16 output gradient's two F(4x4)
-# transforms (the input gradient's V, the weight gradient's dM) by
-# wino_input_f16 + wino_dout_f16 instead of from one read of dY1
-# (ops.wino_dual_f16; B=64 step 1581 / 1586 -> 1596 / 1604 frames/s A/B)
-BF16_DUAL = os.environ.get("NSM_BF16_DUAL", "1") != "0"
-# NSM_LAZY_DY1_F16 (default 1): with BF16_DUAL, the bf16 F(4x4) layers' dY1
-# formed per element inside the dual transform (ops.wino_dual_bn_f16, scale
-# from the finalize's bound) instead of stored by nsm_bn_bwd_apply and read
-# back. At 4 channels per thread that kernel ran at one wave per SIMD and lost
-# (1572 / 1568 vs 1581 / 1580 frames/s); at 2 (BfLane<2>) it wins: B=64 step
-# 1611.6 / 1628.0 / 1616.8 vs 1605.1 / 1609.2 / 1613.3 frames/s, A/B on one box
-LAZY_DY1_F16 = os.environ.get("NSM_LAZY_DY1_F16", "1") != "0"
 # NSM_EVAL_FUSED=0: eval forward with separate BN-apply passes instead of the
 # BN + LeakyReLU (+ skip) in the conv epilogues (nsm_conv_fwd_act)
 EVAL_FUSED = os.environ.get("NSM_EVAL_FUSED", "1") != "0"
-# NSM_UP_WINO=0: materialise the decoder's x2-upsampled input of a Winograd
-# conv (nsm_resize_fwd) instead of sampling it inside the input transform
-UP_IN_WINO = os.environ.get("NSM_UP_WINO", "1") != "0"
-# NSM_WINO_STATS=0: the BN statistics of the Winograd layers by a separate
-# bn_stats pass instead of the output transform
-WINO_BN_STATS = os.environ.get("NSM_WINO_STATS", "1") != "0"
 _WINO_ENV = os.environ.get("NSM_WINO_TILE", "")
 WINO_TILE = int(_WINO_ENV) if _WINO_ENV else 4   # the tile of the VGG stack
 
@@ -118,11 +79,6 @@ F32_MATERIALIZE_ACT = os.environ.get("NSM_F32_ACT", "1") != "0"
 # partials (the reduce pass's dA1 read is gone); 2 (default): per layer, see
 # bnb_mode.
 BNB_MODE = int(os.environ.get("NSM_BNB", "2"))
-# The output BN's backward reduction of blocks 2-8 rides in the kernel that
-# produces their gradient (resize / pooling backward: ops.avgpool2_bwd_add,
-# ops.resize_bwd, ops.up2_resize_bwd with bnred=); NSM_GRAD_BNRED=0 runs the
-# separate nsm_bn_bwd_reduce pass instead
-GRAD_BNRED = os.environ.get("NSM_GRAD_BNRED", "1") != "0"
 # The weight-gradient launches of the Unet backward (GEMM, split reduce,
 # Winograd weight-gradient output) run on a second stream: nothing on the
 # input-gradient path reads them, so they fill its latency-bound launches and
@@ -142,9 +98,6 @@ WGRAD_STREAM = (os.environ.get("NSM_WGRAD_STREAM", "1") != "0"
 # launch gaps) and the bf16 B=64 step gains either way (graph 1627.9-1644.4 vs
 # 1614.1-1629.4)
 GRAPH_SIDE_F32 = int(os.environ.get("NSM_WGRAD_GRAPH_F32", "0"))
-# NSM_WGRAD_PRIO: the side stream's priority (torch.cuda.Stream priority: lower
-# numbers run first; 0 = the default streams')
-WGRAD_PRIO = int(os.environ.get("NSM_WGRAD_PRIO", "0"))
 _wg_stream = None      # the side stream while a Unet backward runs, else None
 _wg_streams = {}       # one side stream per device
 # The tensors the queued side-stream launches read, held (not freed) until the
@@ -178,7 +131,7 @@ def reserve_side_stream(device=None):
            else torch.device("cuda", torch.cuda.current_device()))
     s = _wg_streams.get(dev)
     if s is None:
-        s = _wg_streams[dev] = torch.cuda.Stream(device=dev, priority=WGRAD_PRIO)
+        s = _wg_streams[dev] = torch.cuda.Stream(device=dev)
     buf = torch.empty(64, dtype=torch.int32, device=dev)
     call("nsm_zero_u32", ptr(buf), buf.numel(), stream())
     with torch.cuda.stream(s):
@@ -592,14 +545,14 @@ def _slot(am, i):
 
 
 def _block_slots(amax, k):
-    """Block k's operand-maximum slots of the step's buffer, or None."""
+    """Block k's operand-maximum slots of the step's buffer."""
     w = ops.AMAX_WORDS * AM_PER_BLOCK
-    return None if amax is None else amax[k * w:(k + 1) * w]
+    return amax[k * w:(k + 1) * w]
 
 
 def _x_slot(amax, k):
     """Block k's input-maximum slot (AM_X), filled by the pass that writes
-    block k's input (or the tensor it is resampled from), or None."""
+    block k's input (or the tensor it is resampled from)."""
     return _slot(_block_slots(amax, k), AM_X)
 
 
@@ -609,20 +562,18 @@ def _is_h2(U):
 
 def fuses_resize(blk, dtype, training=True):
     """True when the block's 3x3 conv runs on Winograd and can sample the
-    decoder's x2 upsample inside its input transform (UP_IN_WINO): the fp32
-    layers from WINOGRAD_MIN_CHANNELS, the bf16 path's F(4x4) f16 layers
-    (prep.bf16_wino; nsm_wino_input_f16_resize)."""
+    decoder's x2 upsample inside its input transform, so the upsampled tensor
+    is never written: the fp32 layers from WINOGRAD_MIN_CHANNELS, the bf16
+    path's F(4x4) f16 layers (prep.bf16_wino; nsm_wino_input_f16_resize; in
+    training their weight gradient comes from the kept V, as the block input
+    itself is never materialised)."""
     cip = ops.pad32(blk.conv[0].in_channels)
-    if not UP_IN_WINO:
-        return False
     if dtype == torch.float32:
         return cip >= WINOGRAD_MIN_CHANNELS
-    # (bf16 training: the weight gradient must come from the kept V, as the
-    # block input itself is never materialised)
-    return PREP_BATCH and prep.bf16_wino(cip, dtype, training) and (WGRAD_F16 or not training)
+    return prep.bf16_wino(cip, dtype, training)
 
 
-def _block_eval_fused(blk, xin, B, H, W, pw, name, src_hw, res, am=None):
+def _block_eval_fused(blk, xin, B, H, W, pw, name, src_hw, res, am):
     """Eval: both convs with BN (running statistics) + LeakyReLU (+ the skip
     add) in their epilogues — nothing but A1 and the block output is stored."""
     c0, bn1m, c4, bn2m = blk.conv[0], blk.conv[1], blk.conv[4], blk.conv[5]
@@ -636,7 +587,7 @@ def _block_eval_fused(blk, xin, B, H, W, pw, name, src_hw, res, am=None):
         A1 = ops.conv3x3_wino(xin, B, H, W, pw.U1(tile, False), b1, cip, tile=tile,
                               tag=name + ".conv.0.fwd", src_hw=src_hw, act=(bn1, None),
                               amax_v=_slot(am, AM_V), amax_u=pw.amax_U1(False))
-    elif _has_f16_u(pw) and am is not None:
+    elif _has_f16_u(pw):
         # bf16 eval: Winograd F(4x4) on f16 operands, BN + LeakyReLU in the
         # output transform; the V scale from max|x| (the fused epilogues that
         # wrote x record none; with src_hw, x is the source of the decoder's
@@ -690,28 +641,24 @@ def _block_fwd(blk, X, B, H, W, training, mask, name="", pw=None, src=None, fuse
         U1 = pw.U1(tile, False)
         # h2 U: V is written pre-split, scaled from max|X| (AM_X)
         am_v = _slot(am, AM_X if _is_h2(U1) else AM_V)
-        part1 = None
-        if training and WINO_BN_STATS:
-            # the output transform also writes the BN batch-statistics partials
-            Y1, V, part1 = ops.conv3x3_wino(xin, B, H, W, U1, b1, cip, tile=tile,
-                                            tag=name + ".conv.0.fwd", keep_v=True, stats=True,
-                                            src_hw=src_hw, amax_v=am_v,
-                                            amax_u=pw.amax_U1(False))
-        else:
-            Y1, V = ops.conv3x3_wino(xin, B, H, W, U1, b1, cip, tile=tile,
-                                     tag=name + ".conv.0.fwd", keep_v=True, src_hw=src_hw,
-                                     amax_v=am_v, amax_u=pw.amax_U1(False))
+        # training: the output transform also writes the BN batch-statistics
+        # partials, unless nsm_wino_stat_slots leaves them to the separate pass
+        r = ops.conv3x3_wino(xin, B, H, W, U1, b1, cip, tile=tile, tag=name + ".conv.0.fwd",
+                             keep_v=True, stats=training, src_hw=src_hw, amax_v=am_v,
+                             amax_u=pw.amax_U1(False))
+        Y1, V = r[0], r[1]
+        part1 = r[2] if training else None
         if training and part1 is None:
             part1 = ops.bn_partials(Y1)
     elif _has_f16_u(pw):
         # bf16: Winograd F(4x4) forward on single-plane scaled f16 operands
-        # (src: the decoder's x2 upsample sampled by the input transform)
-        keep = WGRAD_F16 and training
+        # (src: the decoder's x2 upsample sampled by the input transform);
+        # training keeps V for the Winograd-domain weight gradient
         r = ops.conv3x3_wino_f16(xin, B, H, W, pw.Uf16(), b1, cip,
                                  amax=(_slot(am, AM_X), pw.amax_Uf16()), stats=training,
-                                 tag=name + ".conv.0.fwd", keep_v=keep, src_hw=src_hw)
+                                 tag=name + ".conv.0.fwd", keep_v=training, src_hw=src_hw)
         Y1, part1 = r[0], r[1]
-        Vf16 = r[2] if keep else None
+        Vf16 = r[2] if training else None
         if training and part1 is None:
             part1 = ops.bn_partials(Y1)
     else:
@@ -763,7 +710,7 @@ def _block_fwd(blk, X, B, H, W, training, mask, name="", pw=None, src=None, fuse
     s.pw = pw
     s.B, s.H, s.W, s.cip, s.cop = B, H, W, cip, cop
     s.V = V if training else None  # Winograd-domain input, reused by the weight gradient
-    s.Vf16 = Vf16 if training else None  # (the bf16 path's F(4x4) V, likewise)
+    s.Vf16 = Vf16  # (the bf16 path's F(4x4) V, likewise; kept in training only)
     s.A1 = A1 if training else None  # activated 1x1 operand, reused by its weight gradient
     s.Z = None
     s.am = am
@@ -780,7 +727,6 @@ def _block_bwd(blk, s, G, grads, need_dx, name="", gpart=None):
     g = grads
     dtype = G.dtype
     w2d = s.pw.w2(ops.PACK_DGRAD)
-    h2 = s.V is not None and s.V.dtype == ops.H2
     am_dy1 = _slot(s.am, AM_DY1)
     if s.A1 is not None and s.A1.dtype == ops.H2:
         # h2 1x1 operands (csrc/nsm_conv_h2d.inc): the BN backward writes dY2
@@ -798,11 +744,11 @@ def _block_bwd(blk, s, G, grads, need_dx, name="", gpart=None):
         # the dual transform forms dY1 per element (wino_dual_input_bn_h2), so
         # dY1 is never stored and the GEMM never recomputed, under the bound
         # the finalize derives from max|k1 dz| (AM_DY1B)
-        lazy = h2 and need_dx and LAZY_DY1_H2
+        lazy = _is_h2(s.V) and need_dx
         # a direct 3x3 on h2 operands (conv2) takes dY1 as h2 too, written by
         # the BN backward with the bound its finalize derives (AM_DY1B); the
         # recompute form (mode 2) writes fp32 dY1, so it is not used there
-        h2_3x3 = s.X is not None and s.X.dtype == ops.H2
+        h2_3x3 = _is_h2(s.X)
         recompute = not lazy and not h2_3x3 and bnb_mode(s.cip, s.cop, dtype, h2=True) == 2
         if h2_3x3 or lazy:
             am_dy1 = _slot(s.am, AM_DY1B)
@@ -813,7 +759,10 @@ def _block_bwd(blk, s, G, grads, need_dx, name="", gpart=None):
                                           amax_out=None if h2_3x3 or lazy else am_dy1,
                                           h2_out=(_slot(s.am, AM_K1DZ1), am_dy1)
                                           if h2_3x3 or lazy else None, defer=lazy)
-        return _block_bwd_3x3(blk, s, dY1, grads, need_dx, name, h2, am_dy1)
+        return _block_bwd_3x3(blk, s, dY1, grads, need_dx, name, am_dy1)
+    # the weight preparation writes h2 3x3 operands only together with the h2
+    # 1x1 operands handled above (prep.StepWeights)
+    assert not _is_h2(s.V) and not _is_h2(s.X)
     dY2 = ops.bn_bwd(G, s.Y2, s.bn2, HW, None, co, g[bn2m.weight], g[bn2m.bias], g[c4.bias],
                      part=gpart, amax=_slot(s.am, AM_DY2))
     am_w2d = (_slot(s.am, AM_DY2), s.pw.amax_w2(ops.PACK_DGRAD))
@@ -828,43 +777,39 @@ def _block_bwd(blk, s, G, grads, need_dx, name="", gpart=None):
         _wgrad(lambda: ops.conv_wgrad(dY2, s.Y1, B, H, W, 1, ci, co, g[c4.weight], pro=pro,
                                       tag=name + ".conv.4.wgrad"), dY2, s.Y1, *pro)
     mode = bnb_mode(s.cip, s.cop, dtype)
-    if mode == 2 and _wino_f16(s):
+    wino16 = s.Vf16 is not None   # the bf16 path's F(4x4) f16 Winograd
+    if mode == 2 and wino16:
         mode = 1   # dY1 through nsm_bn_bwd_apply, which records max|dY1| (the dgrad's V scale)
-    # pre-split (h2) Winograd operands: dY1's producer records max|dY1|, the
-    # scale source of both its transforms (Vd, dM)
-    # dY1 is consumed only by its two Winograd transforms: leave the BN apply
-    # to the dual transform kernel, dY1 is never stored
-    lazy = s.V is not None and need_dx and DUAL_TRANSFORM and LAZY_DY1 and not h2
-    # bf16 F(4x4): dY1 formed inside the dual transform, scaled from the bound
-    # the finalize derives (AM_DY1B, from max|k1 dz| of the GEMM epilogue)
-    lazy16 = mode == 1 and _wino_f16(s) and need_dx and BF16_DUAL and LAZY_DY1_F16
     if mode:
+        # bf16 F(4x4): dY1 formed inside the dual transform, scaled from the
+        # bound the finalize derives (AM_DY1B, from max|k1 dz| of the GEMM
+        # epilogue), never stored. Elsewhere dY1's producer records max|dY1|
+        # (AM_DY1), the scale source of its consumers.
+        lazy16 = mode == 1 and wino16 and need_dx
         if lazy16:
             am_dy1 = _slot(s.am, AM_DY1B)
         dY1 = ops.conv1x1_dgrad_bn_bwd(dY2, B, H, W, w2d, s.Y1, s.bn1, s.mask, ci, g[bn1m.weight],
                                        g[bn1m.bias], g[c0.bias], mode == 2,
-                                       tag=name + ".conv.4.dgrad", defer=lazy or lazy16,
+                                       tag=name + ".conv.4.dgrad", defer=lazy16,
                                        amax=am_w2d, amax_out=None if lazy16 else am_dy1,
                                        bound=(_slot(s.am, AM_K1DZ1), am_dy1) if lazy16 else None)
     else:
         dA1 = ops.conv_fwd(dY2, B, H, W, w2d, None, s.cip, 1, tag=name + ".conv.4.dgrad",
                            amax=am_w2d)
         dY1 = ops.bn_bwd(dA1, s.Y1, s.bn1, HW, s.mask, ci, g[bn1m.weight], g[bn1m.bias],
-                         g[c0.bias], defer=lazy, amax=am_dy1)
-    return _block_bwd_3x3(blk, s, dY1, grads, need_dx, name, h2, am_dy1)
+                         g[c0.bias], amax=am_dy1)
+    return _block_bwd_3x3(blk, s, dY1, grads, need_dx, name, am_dy1)
 
 
-def _block_bwd_3x3(blk, s, dY1, grads, need_dx, name, h2, am_dy1):
+def _block_bwd_3x3(blk, s, dY1, grads, need_dx, name, am_dy1):
     """The 3x3 conv's weight and input gradients of a DoubleConv from dY1 (the
     gradient wrt its output Y1; a DeferredBnBwd where the dual transform forms
-    it). h2: the forward kept an h2 V (pre-split Winograd operands)."""
+    it), by the path its forward took."""
     c0 = blk.conv[0]
     ci = c0.in_channels
     B, H, W = s.B, s.H, s.W
     g = grads
-    dtype = s.Y1.dtype
-    Vd = None
-    if h2:
+    if _is_h2(s.V):   # Winograd on pre-split (h2) operands
         tile = wino_tile(s.cip, H, W)
         if isinstance(dY1, ops.DeferredBnBwd):
             Vd, dM = ops.wino_dual_input_bn_h2(dY1, s.Y1, s.bn1, s.mask, B, H, W, tile, am_dy1)
@@ -880,24 +825,25 @@ def _block_bwd_3x3(blk, s, dY1, grads, need_dx, name, h2, am_dy1):
         return ops.conv3x3_wino(dY1, B, H, W, s.pw.U1(tile, True), None, s.cip, tile=tile,
                                 tag=name + ".conv.0.dgrad", v_in=Vd, amax_v=am_dy1,
                                 amax_u=s.pw.amax_U1(True))
-    if s.V is not None:
+    if s.V is not None:   # fp32 Winograd
         tile = wino_tile(s.cip, H, W)
-        dM = None
-        if need_dx and DUAL_TRANSFORM:
+        Vd = dM = None
+        if need_dx:
             # dY1's two Winograd transforms (dgrad input, wgrad) from one read
-            am2 = (_slot(s.am, AM_VD), _slot(s.am, AM_DM))
-            if isinstance(dY1, ops.DeferredBnBwd):
-                Vd, dM = ops.wino_dual_input_bn(dY1, s.Y1, s.bn1, s.mask, B, H, W, tile=tile,
-                                                amax=am2)
-            else:
-                Vd, dM = ops.wino_dual_input(dY1, B, H, W, tile=tile, amax=am2)
+            Vd, dM = ops.wino_dual_input(dY1, B, H, W, tile=tile,
+                                         amax=(_slot(s.am, AM_VD), _slot(s.am, AM_DM)))
         V = s.V
         _wgrad(lambda: ops.conv3x3_wgrad_wino(dY1, V, B, H, W, s.cip, ci, ci, g[c0.weight],
                                               tile=tile, tag=name + ".conv.0.wgrad", dM=dM,
                                               amax=(_slot(s.am, AM_DM), _slot(s.am, AM_V))),
                dM, V, dY1 if dM is None else None)
         s.V = V = None
-    elif s.X is not None and s.X.dtype == ops.H2:   # direct 3x3 on h2 operands (dY1 from the BN backward)
+        if not need_dx:
+            return None
+        return ops.conv3x3_wino(dY1, B, H, W, s.pw.U1(tile, True), None, s.cip, tile=tile,
+                                tag=name + ".conv.0.dgrad", v_in=Vd, amax_v=_slot(s.am, AM_VD),
+                                amax_u=s.pw.amax_U1(True))
+    if _is_h2(s.X):   # direct 3x3 on h2 operands (dY1 from the BN backward)
         assert dY1.dtype == ops.H2
         _wgrad(lambda: ops.conv3x3_wgrad_h2(dY1, s.X, B, H, W, ci, ci, g[c0.weight],
                                             tag=name + ".conv.0.wgrad",
@@ -907,10 +853,11 @@ def _block_bwd_3x3(blk, s, dY1, grads, need_dx, name, h2, am_dy1):
         return ops.conv3x3_h2(dY1, B, H, W, s.pw.w1(ops.PACK_DGRAD), None, s.cip, stats=False,
                               amax=(am_dy1, s.pw.amax_w1(ops.PACK_DGRAD)),
                               tag=name + ".conv.0.dgrad")[0]
-    elif s.Vf16 is not None:   # bf16 F(4x4): dY's transform, then the Winograd-domain GEMMs
+    if s.Vf16 is not None:   # bf16 F(4x4): dY's transforms, then the Winograd-domain GEMMs
+        Vd = None
         if isinstance(dY1, ops.DeferredBnBwd):   # dY1 formed per element, never stored
             Vd, dM = ops.wino_dual_bn_f16(dY1, s.Y1, s.bn1, s.mask, B, H, W, am_dy1)
-        elif need_dx and BF16_DUAL:   # with the input gradient's V, from one read of dY1
+        elif need_dx:   # with the input gradient's V, from one read of dY1
             Vd, dM = ops.wino_dual_f16(dY1, B, H, W, am_dy1)
         else:
             dM = ops.wino_dout_f16(dY1, B, H, W, am_dy1)
@@ -919,38 +866,24 @@ def _block_bwd_3x3(blk, s, dY1, grads, need_dx, name, h2, am_dy1):
                                                   g[c0.weight], amax=(am_dy1, _slot(s.am, AM_X)),
                                                   tag=name + ".conv.0.wgrad"), dM, Vf)
         s.Vf16 = Vf = None
-    else:
-        _wgrad(lambda: ops.conv_wgrad(dY1, s.X, B, H, W, 3, ci, ci, g[c0.weight],
-                                      tag=name + ".conv.0.wgrad",
-                                      amax=(am_dy1, _slot(s.am, AM_X))), dY1, s.X)
-    if not need_dx:
-        return None
-    if s.cip >= WINOGRAD_MIN_CHANNELS and dtype == torch.float32:
-        tile = wino_tile(s.cip, H, W)
-        U1d = s.pw.U1(tile, True)
-        return ops.conv3x3_wino(dY1, B, H, W, U1d, None, s.cip, tile=tile,
-                                tag=name + ".conv.0.dgrad", v_in=Vd, amax_v=_slot(s.am, AM_VD),
-                                amax_u=s.pw.amax_U1(True))
-    if _wino_f16(s):   # bf16: Winograd F(4x4) on f16 operands, as the forward
+        if not need_dx:
+            return None
         return ops.conv3x3_wino_f16(dY1, B, H, W, s.pw.Uf16(True), None, s.cip,
                                     amax=(am_dy1, s.pw.amax_Uf16()), stats=False,
                                     tag=name + ".conv.0.dgrad", v_in=Vd)[0]
-    w1d = s.pw.w1(ops.PACK_DGRAD)
-    return ops.conv_fwd(dY1, B, H, W, w1d, None, s.cip, 3, tag=name + ".conv.0.dgrad",
+    _wgrad(lambda: ops.conv_wgrad(dY1, s.X, B, H, W, 3, ci, ci, g[c0.weight],
+                                  tag=name + ".conv.0.wgrad",
+                                  amax=(am_dy1, _slot(s.am, AM_X))), dY1, s.X)
+    if not need_dx:
+        return None
+    return ops.conv_fwd(dY1, B, H, W, s.pw.w1(ops.PACK_DGRAD), None, s.cip, 3,
+                        tag=name + ".conv.0.dgrad",
                         amax=(am_dy1, s.pw.amax_w1(ops.PACK_DGRAD)))
 
 
 def _has_f16_u(pw):
     """The block's weight layouts hold the bf16 path's F(4x4) filters."""
     return getattr(pw, "Uf16", None) is not None and pw.Uf16() is not None
-
-
-def _wino_f16(s):
-    """True when block s's 3x3 runs the bf16 path's F(4x4) f16 Winograd
-    (forward and input gradient; its filters were prepared)."""
-    pw = s.pw
-    return (s.Y1 is not None and s.Y1.dtype == torch.bfloat16
-            and getattr(pw, "Uf16", None) is not None and pw.Uf16(True) is not None)
 
 
 def _bnred_of(s):
@@ -970,9 +903,6 @@ def block_shapes(Rh, Rw):
         enc[k] = (h, w)
         h, w = h // 2, w // 2
     return {**enc, 6: enc[4], 7: enc[3], 8: enc[2], 9: (Rh, Rw)}
-
-
-PREP_BATCH = os.environ.get("NSM_PREP_BATCH", "1") != "0"
 
 
 class FrozenWeights:
@@ -1034,13 +964,10 @@ def _bn_eval(bn_mod, C, c_real, eps, device, gamma, beta):
     return ops.bn_eval(bn_mod, C, c_real, eps, device, gamma=gamma, beta=beta)
 
 
-def _step_weights(mod, dtype, Rh, Rw, training, act_slots=None):
+def _step_weights(mod, dtype, Rh, Rw, training, act_slots):
     """The step's weight layouts, written by ONE prep launch (cached per
     signature; rebuilt when the parameters moved, e.g. FlatAdamW re-homing).
-    act_slots: the forward's activation-maximum slots, zeroed by that launch.
-    NSM_PREP_BATCH=0: None (every block packs its own, one launch per layout)."""
-    if not PREP_BATCH:
-        return None
+    act_slots: the forward's activation-maximum slots, zeroed by that launch."""
     # pre-split (h2) Winograd operands in fp32 training with the f16x2 arithmetic
     h2 = bool(training) and dtype == torch.float32 and H2_WINO and ops.get_f32_split() == 2
     key = (dtype, Rh, Rw, bool(training), WINOGRAD_MIN_CHANNELS, h2)
@@ -1053,8 +980,7 @@ def _step_weights(mod, dtype, Rh, Rw, training, act_slots=None):
     if fz is not None and fz.ready and fz.sws.get(key) is sw:
         # frozen inference weights: the layouts are kept; only the forward's
         # activation-maximum slots need zeroing
-        if act_slots is not None:
-            call("nsm_zero_u32", ptr(act_slots), act_slots.numel(), stream())
+        call("nsm_zero_u32", ptr(act_slots), act_slots.numel(), stream())
         return sw
     if fz is not None:
         fz.sws[key] = sw
@@ -1085,10 +1011,8 @@ class _UnetFn(torch.autograd.Function):
         # producers fill them), zeroed by the weight preparation's first launch
         amax = torch.empty(AM_PER_BLOCK * 10 * ops.AMAX_WORDS, dtype=torch.int32, device=dev)
         sw = _step_weights(mod, cdt, Rh, Rw, training, act_slots=amax)
-        if sw is None:
-            amax = None
-        w1_2 = sw.block(2).w1(ops.PACK_FWD) if sw and ops.pad32(
-            mod.conv2.conv[0].in_channels) < WINOGRAD_MIN_CHANNELS else None
+        w1_2 = (sw.block(2).w1(ops.PACK_FWD)
+                if ops.pad32(mod.conv2.conv[0].in_channels) < WINOGRAD_MIN_CHANNELS else None)
         if w1_2 is not None and w1_2.dtype == ops.H2:
             # conv2's direct 3x3 on h2 operands: X pre-split, scaled from max|x|
             X = ops.input_prep_h2(x32, cin_p, _x_slot(amax, 2))
@@ -1100,24 +1024,22 @@ class _UnetFn(torch.autograd.Function):
         for k in ENCODER:
             with ops.stage(f"conv{k}.fwd"):
                 s = _block_fwd(mod.block(k), inp, B, h, w, training, masks.get(k), f"conv{k}",
-                               pw=sw.block(k) if sw else None, fuse_out=True,
+                               pw=sw.block(k), fuse_out=True,
                                am=_block_slots(amax, k), mask_max=mask_max.get(k, 1.0))
                 saved[k], shapes[k] = s, (h, w)
                 if s.Z is not None:
                     c[k] = s.Z
                     if k < 5:
                         inp = ops.avgpool2(c[k], B, h, w)
-                elif k < 5 and ACT_POOL:   # z and its pooling from one read of Y2
+                elif k < 5:   # z and its pooling from one read of Y2
+                    # (max|c_k| bounds the next block's input, its pooling: the
+                    # scale source of an h2 V)
                     c[k], inp = ops.bn_act_pool(s.Y2, s.bn2, B, h, w, SLOPE,
                                                 amax=_x_slot(amax, k + 1))
-                elif k == 5 and LAZY_DECODER and cdt == torch.bfloat16:
+                elif LAZY_DECODER and cdt == torch.bfloat16:
                     c[k] = ops.Lazy(s.Y2, s.bn2, None)   # sampled by conv6's upsample
-                else:
-                    # max|c_k| bounds the next block's input (its pooling or
-                    # bilinear upsample), the scale source of an h2 V
+                else:   # (max|c_5| likewise bounds conv6's bilinear upsample of it)
                     c[k] = ops.bn_act(s.Y2, s.bn2, SLOPE, amax=_x_slot(amax, k + 1))
-                    if k < 5:
-                        inp = ops.avgpool2(c[k], B, h, w)
                 if k < 5:
                     h, w = h // 2, w // 2
         skip_shape = {6: shapes[4], 7: shapes[3], 8: shapes[2], 9: (Rh, Rw)}
@@ -1137,21 +1059,20 @@ class _UnetFn(torch.autograd.Function):
                 elif fuses_resize(mod.block(k), cdt, training):  # sampled by the input transform
                     if lazy:
                         cur = cur.materialise(SLOPE)
-                        if amax is not None:   # (bn_act of a Lazy records no maximum)
-                            ops.absmax(cur, _x_slot(amax, k))
+                        ops.absmax(cur, _x_slot(amax, k))   # (bn_act of a Lazy records no maximum)
                     up, src = None, (cur, h, w)
                 elif lazy:                 # the previous block output computed on load
                     up = ops.resize_act(cur, B, h, w, h2, w2, SLOPE)
                 else:                      # match is the identity (bitwise, as in ATen)
                     up = ops.resize(cur, B, h, w, h2, w2)
-                if lazy and up is not None and amax is not None:
+                if lazy and up is not None:
                     # the lazy resampling kernels record no maximum: block k's
                     # input-maximum slot (the bf16 F(4x4) V scale) from up itself
                     ops.absmax(up, _x_slot(amax, k))
                 ups[k] = (h, w, h2, w2, th, tw)
                 res = c[SKIP_OF[k]] if k in SKIP_OF else None
                 s = _block_fwd(mod.block(k), up, B, th, tw, training, masks.get(k), f"conv{k}",
-                               pw=sw.block(k) if sw else None, src=src, fuse_out=True, res=res,
+                               pw=sw.block(k), src=src, fuse_out=True, res=res,
                                am=_block_slots(amax, k), mask_max=mask_max.get(k, 1.0))
                 saved[k] = s
                 if s.Z is not None:
@@ -1212,7 +1133,7 @@ class _UnetFn(torch.autograd.Function):
                                  and ctx.saved_blocks[2].Y1.dtype == torch.float32):
             side = _wg_streams.get(dev)
             if side is None:
-                side = _wg_streams[dev] = torch.cuda.Stream(device=dev, priority=WGRAD_PRIO)
+                side = _wg_streams[dev] = torch.cuda.Stream(device=dev)
         _wg_stream = side
         try:
             return _UnetFn._backward(ctx, gout, mod, out, params, flat, grads, views, dp, split)
@@ -1245,10 +1166,8 @@ class _UnetFn(torch.autograd.Function):
                 # conv9 stage 4.43 -> 4.70 ms)
                 if (th, tw) != (h2, w2):
                     dprev, gpart = ops.up2_resize_bwd(dX, B, h, w, th, tw), None
-                elif GRAD_BNRED:
-                    dprev, gpart = ops.resize_bwd(dX, B, h, w, h2, w2, bnred=_bnred_of(sb[k - 1]))
                 else:
-                    dprev, gpart = ops.resize_bwd(dX, B, h, w, h2, w2), None
+                    dprev, gpart = ops.resize_bwd(dX, B, h, w, h2, w2, bnred=_bnred_of(sb[k - 1]))
             # the previous merge / c5 receives dprev; merge_{k-1} = conv + c_skip
             if k - 1 in SKIP_OF:
                 skip_grad[SKIP_OF[k - 1]] = dprev
@@ -1273,11 +1192,9 @@ class _UnetFn(torch.autograd.Function):
                                       blk.conv[5].momentum, blk.conv[5].eps)
             if k > 2:
                 ph, pw = sb[k - 1].H, sb[k - 1].W
-                if GRAD_BNRED:
-                    G, gpart = ops.avgpool2_bwd_add(dX, B, ph, pw, skip_grad.get(k - 1),
-                                                    bnred=_bnred_of(sb[k - 1]))
-                else:
-                    G = ops.avgpool2_bwd_add(dX, B, ph, pw, skip_grad.get(k - 1))
+                # (the pooling backward likewise reduces block k-1's output-BN backward)
+                G, gpart = ops.avgpool2_bwd_add(dX, B, ph, pw, skip_grad.get(k - 1),
+                                                bnred=_bnred_of(sb[k - 1]))
             else:
                 G = dX
             st.__exit__(None, None, None)
