@@ -661,6 +661,40 @@ int nsm_temporal_finalize(const float* psum, const int* pcnt, int npairs, int B,
                           void* stream);
 int nsm_reproject(const float* prev, const float* mv, int B, int C, int H, int W, float scale_x,
                   float scale_y, float* out, unsigned char* valid, void* stream);
+/* ---- feature sensitivity (the paper's §3.2, Eq. 1) --------------------------
+ *   S_i = E[|phi(f_i + eps_i) - phi(f_i)|] / s_i,  eps_i ~ N(0, s_i) per pixel of
+ *   channel i only,  s_i = factor * sigma[i] (formed once in fp32).
+ * The work is a plan of B * (1 + Cs * R) image slots: the B unperturbed images,
+ * then variant (ii, r) of image b at slot B + ((ii * R + r) * B + b); ii runs
+ * over the Cs analysed channels, channel channels[ii] (channels == NULL: ii;
+ * the caller guarantees 0 <= channels[ii] < C), r over the R repeats.
+ * nsm_sens_variants: writes the slots [first, first + n) into out [n,C,H,W]
+ *   (planar fp32, as x [B,C,H,W]): the image's planes, and on the slot's channel
+ *   x + z * s_i with the product rounded before the add. z = noises
+ *   [Cs,R,B,H,W] when given, else a counter-based standard normal keyed by
+ *   (seed, channel, repeat) and counted by (image, pixel), so a variant does not
+ *   depend on first or n. Slots past the plan hold image 0. n * C <= 65535.
+ * nsm_sens_blocks: reduce blocks per image of n output elements (0: unsupported,
+ *   n <= 0 or n near 2^31).
+ * nsm_sens_reduce: out [n_slots][n] are the forward's outputs of the slots
+ *   [first, first + n_slots), base [B][n] those of the unperturbed images. Per
+ *   variant slot v (base and filler slots are skipped) and block:
+ *   psum[(v * blocks + block) * 2 + {0, 1}] = sum |o - base_b|, sum (o - base_b),
+ *   fp32 in a fixed tree of 11 levels. No atomics.
+ * nsm_sens_finalize: one block, in double and in a fixed order: terms (may be
+ *   NULL) [Cs,R,B,2] = the two sums per variant; acc [Cs][3] (device doubles,
+ *   zeroed by the caller before the first batch) += {sum |d|, sum d, R * B * n};
+ *   absolute[i] = acc0 / (acc2 * s_i), sgn[i] = acc1 / (acc2 * s_i),
+ *   relative[i] = absolute[i] / sum_j absolute[j], over everything accumulated. */
+int nsm_sens_blocks(int64_t n);
+int nsm_sens_variants(const float* x, const float* sigma, const int* channels,
+                      const float* noises, uint64_t seed, int B, int C, int H, int W, int Cs,
+                      int R, float factor, int first, int n, float* out, void* stream);
+int nsm_sens_reduce(const float* out, const float* base, int first, int n_slots, int B, int Cs,
+                    int R, int64_t n, float* psum, void* stream);
+int nsm_sens_finalize(const float* psum, int Cs, int R, int B, int64_t n, const float* sigma,
+                      const int* channels, float factor, float* terms, double* acc,
+                      float* absolute, float* sgn, float* relative, void* stream);
 /* PerturbationLoss.perturb_input (pert_loss.py:26-59):
  * per-channel unbiased std over the batch of NCHW x -> std[C] */
 int nsm_channel_std(const float* x, int B, int C, int H, int W, float* partial, float* std,

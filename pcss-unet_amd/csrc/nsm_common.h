@@ -288,6 +288,25 @@ __device__ __forceinline__ void h2_store8(bf16_t* row, int c, F8 v, float s) {
   *(u32x4*)(row + 2 * c + 8) = u32x4{la.x, la.y, lb.x, lb.y};
 }
 
+// ---- counter-based normal generator (nsm_tail.hip, nsm_sensitivity.hip) ------
+// standard normal from (seed, counter): splitmix64 -> two uniforms -> Box-Muller.
+// Contraction is off inside, as in the units that use it, so every includer
+// gets the same bits.
+__device__ __forceinline__ uint64_t mix64(uint64_t z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+__device__ __forceinline__ float gauss_hash(uint64_t seed, uint64_t ctr) {
+#pragma clang fp contract(off)
+  const uint64_t r = mix64(seed ^ mix64(ctr));
+  const float u1 = ((float)(uint32_t)(r >> 40) + 1.f) * (1.f / 16777217.f);  // (0, 1]
+  const float u2 = (float)(uint32_t)(r & 0xFFFFFFu) * (1.f / 16777216.f);
+  return sqrtf(-2.f * logf(u1)) * cosf(6.28318530718f * u2);
+}
+
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // ---- environment knobs (host) ------------------------------------------------

@@ -222,21 +222,6 @@ __global__ void __launch_bounds__(1024) tail_decide_kernel(const int64_t* __rest
   }
 }
 
-// standard normal from (seed, counter): splitmix64 -> two uniforms -> Box-Muller
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ float gauss_hash(uint64_t seed, uint64_t ctr) {
-  const uint64_t r = mix64(seed ^ mix64(ctr));
-  const float u1 = ((float)(uint32_t)(r >> 40) + 1.f) * (1.f / 16777217.f);  // (0, 1]
-  const float u2 = (float)(uint32_t)(r & 0xFFFFFFu) * (1.f / 16777216.f);
-  return sqrtf(-2.f * logf(u1)) * cosf(6.28318530718f * u2);
-}
-
 // ---- K3: repair (main.py:320-354), only when K2 decided so -------------------
 // NaN -> mean + randn * std * 0.1 ; +-Inf -> sign * max|valid| * 10.
 // `noise` (optional, flat like g) supplies the randn values for parity tests;

@@ -15,6 +15,8 @@ from .optim import (FlatAdam, FlatAdamW, FlatSGD, allreduce_grads, flat_grad,  #
                     make_optimizer)
 from .grad_scaler import GradScaler  # noqa: F401
 from .infer import GraphedUnet  # noqa: F401
+from .sensitivity import (FeatureSensitivity, SensitivityResult,  # noqa: F401
+                          feature_sensitivity)
 from .step import GraphedTrainStep  # noqa: F401
 from .vgg import MultiLayerVGGLoss  # noqa: F401
 
