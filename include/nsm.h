@@ -661,6 +661,26 @@ int nsm_temporal_finalize(const float* psum, const int* pcnt, int npairs, int B,
                           void* stream);
 int nsm_reproject(const float* prev, const float* mv, int B, int C, int H, int W, float scale_x,
                   float scale_y, float* out, unsigned char* valid, void* stream);
+/* The temporal anti-aliasing resolve of one frame (the paper's "TAA (1 last
+ * frame)" column of Figure 6), one launch, on the lookup and the rejection tests
+ * above (the same device functions). cur [B,C,H,W]: the frame; hist [B,C,H,W]:
+ * the previous RESOLVED frame; depth_prev / normal_prev: the previous INPUT
+ * frame's. Per pixel p and channel:
+ *   h = bilinear sample of hist at m(p);
+ *   clamp != 0: h = min(max(h, lo), hi), lo / hi = min / max of cur over the 3x3
+ *     neighbourhood of p, row and column indices clamped (edge replicate);
+ *   out = accepted(p) ? fmaf(1 - blend, h - cur, cur) : cur,
+ * blend in (0, 1] being the weight of the current frame: out is cur bit for bit
+ * where h == cur and when blend == 1. accepted (may be NULL) [B,1,H,W]: 1 where
+ * the history was used. mv, the depth pair and the normal pair may be NULL as in
+ * nsm_temporal_pair (mv == NULL: no motion, nothing rejected). out must be
+ * neither hist nor cur: other threads gather from both. Shapes as
+ * nsm_temporal_blocks allows. No atomics, no allocation, no synchronisation. */
+int nsm_taa_resolve(const float* cur, const float* hist, const float* mv, const float* depth_cur,
+                    const float* depth_prev, const float* normal_cur, const float* normal_prev,
+                    int B, int C, int H, int W, float scale_x, float scale_y, float blend,
+                    int clamp, float depth_tol, float normal_cos, float* out,
+                    unsigned char* accepted, void* stream);
 /* ---- feature sensitivity (the paper's §3.2, Eq. 1) --------------------------
  *   S_i = E[|phi(f_i + eps_i) - phi(f_i)|] / s_i,  eps_i ~ N(0, s_i) per pixel of
  *   channel i only,  s_i = factor * sigma[i] (formed once in fp32).

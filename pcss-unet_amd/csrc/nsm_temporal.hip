@@ -1,6 +1,7 @@
 // The temporal-instability metric with motion-vector reprojection (the paper's
 // Eq. 3; pert_loss.py:170-199 takes `motion_vectors` and leaves their branch as
-// `pass`), and the reprojection as an op of its own. Planar NCHW fp32.
+// `pass`), the reprojection as an op of its own, and the temporal anti-aliasing
+// resolve on the same lookup (taa_resolve_kernel below). Planar NCHW fp32.
 //   D_t(p) = |I_t(p) - I_{t-1}(m(p))|,  E = mean(exp(alpha D) - 1)
 //   m(p) = (x + mv[b,0,y,x] * scale_x, y + mv[b,1,y,x] * scale_y) in pixels,
 //   integer coordinates are pixel centres (align_corners=True), bilinear.
@@ -109,25 +110,15 @@ __device__ __forceinline__ void thread_taps(const float* __restrict__ mv, int H,
   }
 }
 
-// psum[blk], pcnt[blk]: the block's sum of exp(alpha D) - 1 over its surviving
-// elements and their number. zc/zp (depth of the current / previous frame,
-// [B,1,H,W]) and nc/np (normals, [B,3,H,W]) may be NULL in pairs.
-__global__ void __launch_bounds__(TP_THREADS)
-    temporal_pair_kernel(const float* __restrict__ cur, const float* __restrict__ prev,
-                         const float* __restrict__ mv, const float* __restrict__ zc,
-                         const float* __restrict__ zp, const float* __restrict__ nc,
-                         const float* __restrict__ np, int C, int H, int W, FastDiv dw, int per,
-                         float scale_x, float scale_y, float alpha, float depth_tol,
-                         float normal_cos, float* __restrict__ psum, int* __restrict__ pcnt) {
-  __shared__ float shs[TP_THREADS / 64];
-  __shared__ int shc[TP_THREADS / 64];
-  const uint32_t HW = (uint32_t)H * W;
-  int b;
-  uint32_t blk;
-  Taps t[TP_VEC];
-  thread_taps(mv, H, W, dw, per, scale_x, scale_y, b, blk, t);
-  float s = 0.f;
-  int cnt = 0;
+// The depth and normal tests of the thread's pixels (the metric and the TAA
+// pass share them): zc/zp [B,1,H,W] and nc/np [B,3,H,W] of the current /
+// previous frame, NULL in pairs; a failed test clears t[j].ok.
+__device__ __forceinline__ void reject_taps(const float* __restrict__ zc,
+                                            const float* __restrict__ zp,
+                                            const float* __restrict__ nc,
+                                            const float* __restrict__ np, int b, uint32_t blk,
+                                            uint32_t HW, float depth_tol, float normal_cos,
+                                            Taps (&t)[TP_VEC]) {
   float v[TP_VEC];
   if (zc) {
     ld_pix(zc + (size_t)b * HW, blk, HW, v);
@@ -149,6 +140,29 @@ __global__ void __launch_bounds__(TP_THREADS)
     for (int j = 0; j < TP_VEC; ++j)
       t[j].ok = t[j].ok && dot[j] >= normal_cos;
   }
+}
+
+// psum[blk], pcnt[blk]: the block's sum of exp(alpha D) - 1 over its surviving
+// elements and their number. zc/zp (depth of the current / previous frame,
+// [B,1,H,W]) and nc/np (normals, [B,3,H,W]) may be NULL in pairs.
+__global__ void __launch_bounds__(TP_THREADS)
+    temporal_pair_kernel(const float* __restrict__ cur, const float* __restrict__ prev,
+                         const float* __restrict__ mv, const float* __restrict__ zc,
+                         const float* __restrict__ zp, const float* __restrict__ nc,
+                         const float* __restrict__ np, int C, int H, int W, FastDiv dw, int per,
+                         float scale_x, float scale_y, float alpha, float depth_tol,
+                         float normal_cos, float* __restrict__ psum, int* __restrict__ pcnt) {
+  __shared__ float shs[TP_THREADS / 64];
+  __shared__ int shc[TP_THREADS / 64];
+  const uint32_t HW = (uint32_t)H * W;
+  int b;
+  uint32_t blk;
+  Taps t[TP_VEC];
+  thread_taps(mv, H, W, dw, per, scale_x, scale_y, b, blk, t);
+  float s = 0.f;
+  int cnt = 0;
+  float v[TP_VEC];
+  reject_taps(zc, zp, nc, np, b, blk, HW, depth_tol, normal_cos, t);
   for (int c = 0; c < C; ++c) {
     const size_t plane = ((size_t)b * C + c) * HW;
     ld_pix(cur + plane, blk, HW, v);
@@ -277,6 +291,88 @@ __global__ void __launch_bounds__(TP_THREADS)
   }
 }
 
+// The temporal anti-aliasing resolve of one frame (the paper's "TAA (1 last
+// frame)" baseline of Figure 6), same grid and slots as temporal_pair_kernel:
+//   h = bilinear sample of hist (the previous RESOLVED frame) at m(p),
+//   clamp: h = min(max(h, lo), hi), lo/hi = min/max of cur over the 3x3
+//   neighbourhood of p, row and column indices clamped (edge replicate: the
+//   neighbourhood never leaves the plane, whatever the block seam),
+//   out = accepted ? fmaf(keep, h - cur, cur) : cur,  keep = 1 - blend,
+// which is cur bit for bit when h == cur and when blend == 1. accepted (may be
+// NULL) [B,1,H,W]: 1 where the history was used. The verdicts come from the
+// previous INPUT frame's depth and normals (reject_taps), not from hist.
+// The neighbourhood is eight more loads per pixel and channel, all of them on
+// lines the wave's own row runs and its neighbours' bring into the cache (an
+// LDS copy of the rows a block spans measured 1.2 to 1.9 times slower:
+// DESIGN.md, "Temporal anti-aliasing pass").
+__global__ void __launch_bounds__(TP_THREADS)
+    taa_resolve_kernel(const float* __restrict__ cur, const float* __restrict__ hist,
+                       const float* __restrict__ mv, const float* __restrict__ zc,
+                       const float* __restrict__ zp, const float* __restrict__ nc,
+                       const float* __restrict__ np, int C, int H, int W, FastDiv dw, int per,
+                       float scale_x, float scale_y, float keep, int clamp, float depth_tol,
+                       float normal_cos, float* __restrict__ out,
+                       unsigned char* __restrict__ accepted) {
+  const uint32_t HW = (uint32_t)H * W;
+  int b;
+  uint32_t blk;
+  Taps t[TP_VEC];
+  thread_taps(mv, H, W, dw, per, scale_x, scale_y, b, blk, t);
+  reject_taps(zc, zp, nc, np, b, blk, HW, depth_tol, normal_cos, t);
+  if (accepted) {
+    unsigned char* ab = accepted + (size_t)b * HW;
+#pragma unroll
+    for (int j = 0; j < TP_VEC; ++j) {
+      const uint32_t p = slot_pixel(blk, j);
+      if (p < HW) ab[p] = t[j].ok ? 1 : 0;
+    }
+  }
+  // plane offsets of the rows above, of and below each pixel and its columns
+  // to the left and right (a slot past the plane's end uses the last pixel's)
+  int r0[TP_VEC], r1[TP_VEC], r2[TP_VEC], xl[TP_VEC], xc[TP_VEC], xr[TP_VEC];
+  if (clamp) {
+#pragma unroll
+    for (int j = 0; j < TP_VEC; ++j) {
+      const uint32_t p = min(slot_pixel(blk, j), HW - 1);
+      const int y = (int)fdiv(p, dw), x = (int)p - y * W;
+      r0[j] = max(y - 1, 0) * W;
+      r1[j] = y * W;
+      r2[j] = min(y + 1, H - 1) * W;
+      xl[j] = max(x - 1, 0);
+      xc[j] = x;
+      xr[j] = min(x + 1, W - 1);
+    }
+  }
+  for (int c = 0; c < C; ++c) {
+    const size_t plane = ((size_t)b * C + c) * HW;
+    float v[TP_VEC], h[TP_VEC];
+    ld_pix(cur + plane, blk, HW, v);
+#pragma unroll
+    for (int j = 0; j < TP_VEC; ++j) h[j] = tap_sample(hist + plane, t[j]);
+    if (clamp) {
+      const float* src = cur + plane;
+#pragma unroll
+      for (int j = 0; j < TP_VEC; ++j) {
+        const float *a = src + r0[j], *m = src + r1[j], *z = src + r2[j];
+        const float a0 = a[xl[j]], a1 = a[xc[j]], a2 = a[xr[j]];
+        const float m0 = m[xl[j]], m2 = m[xr[j]];
+        const float z0 = z[xl[j]], z1 = z[xc[j]], z2 = z[xr[j]];
+        const float lo = fminf(fminf(fminf(a0, a1), fminf(a2, m0)),
+                               fminf(fminf(m2, z0), fminf(fminf(z1, z2), v[j])));
+        const float hi = fmaxf(fmaxf(fmaxf(a0, a1), fmaxf(a2, m0)),
+                               fmaxf(fmaxf(m2, z0), fmaxf(fmaxf(z1, z2), v[j])));
+        h[j] = fminf(fmaxf(h[j], lo), hi);
+      }
+    }
+    float* o = out + plane;
+#pragma unroll
+    for (int j = 0; j < TP_VEC; ++j) {
+      const uint32_t p = slot_pixel(blk, j);
+      if (p < HW) o[p] = t[j].ok ? fmaf(keep, h[j] - v[j], v[j]) : v[j];
+    }
+  }
+}
+
 // fp32 holds pixel coordinates exactly below 2^24; C*H*W < 2^31 keeps every
 // plane offset in an int and every block count in an int
 static bool temporal_shape_ok(int B, int C, int H, int W) {
@@ -326,6 +422,32 @@ extern "C" int nsm_temporal_finalize(const float* psum, const int* pcnt, int npa
                      psum, pcnt, npairs, B, per, (long long)all_count, sums, (long long*)counts, out,
                      acc);
   NSM_LAUNCH_CHECK("temporal_finalize");
+  return 0;
+}
+
+extern "C" int nsm_taa_resolve(const float* cur, const float* hist, const float* mv,
+                               const float* depth_cur, const float* depth_prev,
+                               const float* normal_cur, const float* normal_prev, int B, int C,
+                               int H, int W, float scale_x, float scale_y, float blend, int clamp,
+                               float depth_tol, float normal_cos, float* out,
+                               unsigned char* accepted, void* stream) {
+  NSM_CHECK_ARG(cur && hist && out, "taa_resolve: null pointer");
+  NSM_CHECK_ARG(out != hist && out != cur,
+                "taa_resolve: out is %s (other threads gather from it)",
+                out == hist ? "hist" : "cur");
+  NSM_CHECK_ARG(blend > 0.f && blend <= 1.f, "taa_resolve: blend %g is not in (0, 1]",
+                (double)blend);
+  NSM_CHECK_ARG(!depth_cur == !depth_prev && !normal_cur == !normal_prev,
+                "taa_resolve: depth and normals come for both frames or for none");
+  NSM_CHECK_ARG(mv || (!depth_cur && !normal_cur),
+                "taa_resolve: depth or normal rejection without motion vectors");
+  NSM_CHECK_ARG(temporal_shape_ok(B, C, H, W), "taa_resolve: shape %d x %d x %d x %d", B, C, H, W);
+  const int per = nsm_temporal_blocks(B, C, H, W);
+  hipLaunchKernelGGL(taa_resolve_kernel, dim3(B * per), dim3(TP_THREADS), 0, as_stream(stream), cur,
+                     hist, mv, depth_cur, depth_prev, normal_cur, normal_prev, C, H, W,
+                     make_fastdiv((uint32_t)W), per, scale_x, scale_y, 1.f - blend, clamp,
+                     depth_tol, normal_cos, out, accepted);
+  NSM_LAUNCH_CHECK("taa_resolve");
   return 0;
 }
 

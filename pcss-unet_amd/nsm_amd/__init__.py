@@ -11,6 +11,7 @@ from .losses import (CustomLoss, EnhancedCustomLoss, L1Loss, PerturbationLoss,  
                      ssim_loss)
 from .temporal import (TemporalInstability, reproject,  # noqa: F401
                        temporal_instability_terms)
+from .taa import TemporalAA, taa_resolve, temporal_aa  # noqa: F401
 from .optim import (FlatAdam, FlatAdamW, FlatSGD, allreduce_grads, flat_grad,  # noqa: F401
                     make_optimizer)
 from .grad_scaler import GradScaler  # noqa: F401

@@ -36,17 +36,17 @@ def _f32(t, device=None):
     return t.to(device=device, dtype=torch.float32) if device is not None else t.to(torch.float32)
 
 
-def _seq(x, what, n, shape):
+def _seq(x, what, n, shape, who="temporal instability"):
     """A list of n tensors of `shape` from a list or a stacked tensor (ValueError otherwise)."""
     if x is None:
         return None
     if len(x) != n:
-        raise ValueError(f"temporal instability: {what} has {len(x)} entries, expected {n}")
+        raise ValueError(f"{who}: {what} has {len(x)} entries, expected {n}")
     out = [x[i] for i in range(n)]
     for i, t in enumerate(out):
         if not torch.is_tensor(t) or tuple(t.shape) != tuple(shape):
             got = tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
-            raise ValueError(f"temporal instability: {what}[{i}] is {got}, expected {tuple(shape)}")
+            raise ValueError(f"{who}: {what}[{i}] is {got}, expected {tuple(shape)}")
     return out
 
 
