@@ -715,6 +715,28 @@ int nsm_sens_reduce(const float* out, const float* base, int first, int n_slots,
 int nsm_sens_finalize(const float* psum, int Cs, int R, int B, int64_t n, const float* sigma,
                       const int* channels, float factor, float* terms, double* acc,
                       float* absolute, float* sgn, float* relative, void* stream);
+/* ---- dataset channel statistics (train_stats.json, the sigma of Eq. 1) --------
+ * Per channel, over every pixel of every frame fed in: a record of 6 doubles
+ *   {count, mean, M2, min, max, nonfinite},
+ * M2 the sum of squared deviations from that mean (variance = M2 / count).
+ * Non-finite samples are counted in `nonfinite` and left out of the other five;
+ * a record without a finite sample is {0, 0, 0, +inf, -inf, k}. Records merge by
+ * Chan's pairwise rule in fp64, in a fixed order: the same call sequence gives
+ * the same bits. No atomics, no host synchronisation, no allocation.
+ * nsm_stats_blocks: records per plane of hw elements (0: hw < 1 or hw >= 2^31).
+ * nsm_stats_partial: x [B][C][HW] fp32, contiguous, 4-byte aligned (no more is
+ *   assumed: ragged heads and tails of the 16-byte loads are handled inside);
+ *   records [B * C * nsm_stats_blocks(HW)][6], block after block of each plane.
+ * nsm_stats_merge: folds records [B][C][per][6]: the `per` records of a plane in
+ *   index order (runs of neighbours, then a fixed tree of neighbouring runs)
+ *   into the frame's record (written to frames [B][C][6] unless NULL), then the
+ *   frames in order, 8 at a time by the same tree, into state [C][6], which the caller
+ *   initialises to empty records and keeps across batches. With per = 1 and
+ *   B = 1 it merges another accumulator's state. */
+int nsm_stats_blocks(int64_t hw);
+int nsm_stats_partial(const float* x, int B, int C, int64_t HW, double* records, void* stream);
+int nsm_stats_merge(const double* records, int B, int C, int per, double* frames, double* state,
+                    void* stream);
 /* PerturbationLoss.perturb_input (pert_loss.py:26-59):
  * per-channel unbiased std over the batch of NCHW x -> std[C] */
 int nsm_channel_std(const float* x, int B, int C, int H, int W, float* partial, float* std,

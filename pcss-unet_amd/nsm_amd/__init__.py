@@ -18,6 +18,8 @@ from .grad_scaler import GradScaler  # noqa: F401
 from .infer import GraphedUnet  # noqa: F401
 from .sensitivity import (FeatureSensitivity, SensitivityResult,  # noqa: F401
                           feature_sensitivity)
+from .stats import (ChannelStats, StatsResult, channel_stats, dataset_stats,  # noqa: F401
+                    save_stats, stats_json)
 from .step import GraphedTrainStep  # noqa: F401
 from .vgg import MultiLayerVGGLoss  # noqa: F401
 

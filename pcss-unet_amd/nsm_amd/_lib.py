@@ -138,6 +138,9 @@ _SIGS = {
     "nsm_sens_variants": (I, [P, P, P, P, U64, I, I, I, I, I, I, F, I, I, P, P]),
     "nsm_sens_reduce": (I, [P, P, I, I, I, I, I, L, P, P]),
     "nsm_sens_finalize": (I, [P, I, I, I, L, P, P, F, P, P, P, P, P, P]),
+    "nsm_stats_blocks": (I, [L]),
+    "nsm_stats_partial": (I, [P, I, I, L, P, P]),
+    "nsm_stats_merge": (I, [P, I, I, I, P, P, P]),
     "nsm_channel_std": (I, [P, I, I, I, I, P, P, P]),
     "nsm_perturb": (I, [P, P, P, I, I, I, I, F, P, P]),
     "nsm_sumsq": (I, [P, L, P, P, P]),

@@ -16,6 +16,8 @@ data-parallel sharding of it.
   nsm_loader_*: mmap + host threads staging upcoming batches in pinned
   memory + async H2D on the compute stream), normalised on the GPU
   (nsm_normalize_frames) — the production input path.
+  `stats=` takes the figures directly (a StatsResult of nsm_amd/stats.py or a
+  (means, stds) pair) in place of the train_stats.json lookup.
 """
 import json
 import os
@@ -40,6 +42,23 @@ def load_stats(stats_dir, channels=None):
         return None
     return (torch.tensor(st["means"], dtype=torch.float32),
             torch.tensor(st["stds"], dtype=torch.float32))
+
+
+def _given_stats(stats, channels):
+    """(means, stds) as float32 tensors from a StatsResult (nsm_amd/stats.py) or a
+    (means, stds) pair of tensors or sequences: what load_stats gives for the
+    train_stats.json holding the same figures."""
+    if hasattr(stats, "means") and hasattr(stats, "stds"):
+        stats = (stats.means, stats.stds)
+    try:
+        means, stds = stats
+    except (TypeError, ValueError):
+        raise ValueError("stats must be a StatsResult or a (means, stds) pair") from None
+    out = tuple(torch.as_tensor(v).detach().to(torch.float32).reshape(-1) for v in (means, stds))
+    for v in out:
+        if v.numel() != channels:
+            raise ValueError(f"stats has {v.numel()} entries, the frames have {channels} channels")
+    return out
 
 
 class MmapLiverDataset(torch.utils.data.Dataset):
@@ -122,7 +141,7 @@ class FrameLoader:
     over epochs. len() = batches per epoch."""
 
     def __init__(self, data_dir, split="train", batch=8, device="cuda", world=1, rank=0,
-                 stats_dir=None, apply_normalization=True, slots=3, threads=4):
+                 stats_dir=None, apply_normalization=True, slots=3, threads=4, stats=None):
         from ._lib import NsmError, call, last_error, lib
         self._lib, self._call = lib, call
         self.device = torch.device(device)
@@ -140,7 +159,8 @@ class FrameLoader:
         self.nbatches = int(lib.nsm_loader_batches(h))
         self.norm = None
         if apply_normalization:
-            st = load_stats(stats_dir or data_dir, self.C)
+            st = _given_stats(stats, self.C) if stats is not None else \
+                load_stats(stats_dir or data_dir, self.C)
             if st is not None:
                 self.norm = (st[0].to(self.device), st[1].to(self.device))
 

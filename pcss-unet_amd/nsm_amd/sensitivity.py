@@ -24,7 +24,8 @@ results are device tensors, and reading them is the only wait.
 `sigma`: a [C] tensor or sequence, one float for every channel, or "batch" for
 the unbiased per-channel std of the given batch (nsm_channel_std, what
 PerturbationLoss.perturb_input uses). Inputs normalised by FrameLoader have a
-dataset sigma of 1.
+dataset sigma of 1. For raw inputs the paper's sigma_i ("aggregating all pixels
+in the dataset") is dataset_stats(...).stds or ChannelStats (nsm_amd/stats.py).
 """
 from collections import namedtuple
 
