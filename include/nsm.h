@@ -1016,6 +1016,45 @@ void nsm_loader_destroy(void* loader);
 int nsm_normalize_frames(float* x, int B, int C, int64_t HW, const float* mean, const float* stdv,
                          float eps, void* stream);
 
+/* ---- inference frame path (inference.py process_image / save_output) ----------
+ * What the reference wraps around model(x) per frame, as two streaming passes
+ * (csrc/nsm_frame.hip): one read of the source, one write of each output, no
+ * atomics, no host synchronisation, no allocation; capturable like every entry.
+ * scrub(v): NaN -> 0, +Inf -> 1, -Inf -> 0 (torch.nan_to_num(nan=0.0, posinf=1.0,
+ *   neginf=0.0), inference.py:173,202); a finite v keeps its bits (-0.0,
+ *   denormals and FLT_MAX included).
+ * nsm_frame_prep: x [B][C][H][W] fp32 -> out [B][C][Hp][Wp] fp32, Hp >= H,
+ *   Wp >= W: out[b,c,y,x] = f(x[b,c,ry,rx]), ry = y < H ? y : 2 * (H - 1) - y and
+ *   rx likewise, i.e. nn.ReflectionPad2d((0, Wp - W, 0, Hp - H))
+ *   (inference.py:153-163), which needs Hp - H < H and Wp - W < W. f scrubs when
+ *   scrub != 0 (inference.py:170-173) and then, when mean / stdv [C] are given
+ *   (both or neither), normalises: (v - mean[c]) / (stdv[c] + eps), the
+ *   expression and the bits of nsm_normalize_frames (setdata.py:316). NULL:
+ *   no normalisation, which is inference.py. Census (partial and report both or
+ *   neither): report[b][0..2] = the NaN, +Inf and -Inf among the C*H*W source
+ *   samples of image b (a padded copy is not counted); partial holds
+ *   B * nsm_frame_blocks(C, Hp, Wp) * 3 words.
+ * nsm_frame_finish: o [B][C][Hp][Wp] fp32 (the network's output), its top-left
+ *   H x W (H <= Hp, W <= Wp), C = 1, 3 or 4 (the cases of save_output,
+ *   inference.py:111-128): v' = clip(scrub(v), 0, 1) (inference.py:199-202, :109).
+ *   u8 [B][H][W][C] = (uint8_t)(v' * 255.0f): one fp32 multiply, then truncation,
+ *   as (output * 255).astype(np.uint8) (inference.py:115-125, infer.py:79,
+ *   main.py:457); f32 [B][C][H][W] = v'. Either output may be NULL, not both.
+ *   Census: report[b][3..5] = the non-finite, the < 0 and the > 1 samples
+ *   (-Inf and +Inf count in both of theirs) of the cropped region before the
+ *   scrub and the clip; partial holds B * nsm_frame_blocks(1, H, W) * 3 words.
+ * nsm_frame_blocks: blocks per image of a pass over C planes of H x W (0: a
+ *   dimension < 1, or C*H*W >= 2^31). report is [B][6] int32; the census
+ *   finalize runs in the same call, behind the pass, and adds an image's
+ *   partial counts in a fixed order. Pointers are 4-byte aligned (u8: any);
+ *   16-byte accesses are used wherever an address allows. */
+int nsm_frame_blocks(int C, int H, int W);
+int nsm_frame_prep(const float* x, int B, int C, int H, int W, int Hp, int Wp, const float* mean,
+                   const float* stdv, float eps, int scrub, float* out, uint32_t* partial,
+                   int32_t* report, void* stream);
+int nsm_frame_finish(const float* o, int B, int C, int Hp, int Wp, int H, int W, uint8_t* u8,
+                     float* f32, uint32_t* partial, int32_t* report, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@ from .optim import (FlatAdam, FlatAdamW, FlatSGD, allreduce_grads, flat_grad,  #
                     make_optimizer)
 from .grad_scaler import GradScaler  # noqa: F401
 from .infer import GraphedUnet  # noqa: F401
+from .frames import FramePipeline, finish_frames, prepare_frames  # noqa: F401
 from .sensitivity import (FeatureSensitivity, SensitivityResult,  # noqa: F401
                           feature_sensitivity)
 from .stats import (ChannelStats, StatsResult, channel_stats, dataset_stats,  # noqa: F401

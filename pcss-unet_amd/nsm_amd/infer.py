@@ -33,26 +33,35 @@ from ._lib import require_gpu
 
 class GraphedUnet:
     def __init__(self, model, example, warmup=2, static_weights=True):
-        from .unet import FrozenWeights
         require_gpu(example, "GraphedUnet example input")
+        self.shape, self.dtype = tuple(example.shape), example.dtype
+        self.static_in = example.detach().clone()
+        self._capture(model, warmup, static_weights)
+
+    def _body(self):
+        """What the graph holds, from static_in to the static output. A subclass
+        puts passes of its own around the forward (frames.FramePipeline) and
+        shares the capture and the weight handling below."""
+        return self.model(self.static_in)
+
+    def _capture(self, model, warmup, static_weights):
+        from .unet import FrozenWeights
         self.model = model
         self.was_training = model.training
         model.eval()
-        self.shape, self.dtype = tuple(example.shape), example.dtype
-        self.static_in = example.detach().clone()
         self.frozen = FrozenWeights(model) if static_weights else None
-        side = torch.cuda.Stream(device=example.device)
+        side = torch.cuda.Stream(device=self.static_in.device)
         side.wait_stream(torch.cuda.current_stream())
         if self.frozen is not None:
             self.frozen.__enter__()
         try:
             with torch.cuda.stream(side), torch.no_grad():
                 for _ in range(warmup):           # settle the caching allocator (and the layouts)
-                    model(self.static_in)
+                    self._body()
             torch.cuda.current_stream().wait_stream(side)
             self.graph = torch.cuda.CUDAGraph()
             with torch.no_grad(), torch.cuda.graph(self.graph):
-                self.static_out = model(self.static_in)
+                self.static_out = self._body()
         finally:
             if self.frozen is not None:
                 self.frozen.__exit__(None, None, None)
