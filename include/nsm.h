@@ -744,6 +744,47 @@ int nsm_channel_std(const float* x, int B, int C, int H, int W, float* partial, 
 /* out = x + noise * std[c] * factor */
 int nsm_perturb(const float* x, const float* noise, const float* std, int B, int C, int H,
                 int W, float factor, float* out, void* stream);
+/* ---- the perturbation-loss step (the paper's §3.3, Eq. 2) -------------------
+ * Asynchronous on `stream`; no allocation, no synchronisation, no atomics;
+ * the same call gives the same bits.
+ * nsm_perturb_variants: the P (1..NSM_PERT_MAX) perturbed copies of x
+ *   [B,C,H,W] into out [P,B,C,H,W] from one launch and one read of x:
+ *     out[i] = x + (z * std[c]) * factor,
+ *   the product z * std[c] rounded to fp32, then one fused multiply-add: with
+ *   the same z the bits are nsm_perturb's. std [C] as nsm_channel_std writes it.
+ *   z = noises [P,B,C,H,W] when given, else a counter-based standard normal
+ *   keyed by (seed, variant i) and counted by (b * C + c) * H*W + pixel: variant
+ *   i of a call does not depend on P nor on the launch geometry. seed_dev
+ *   (int64[1], device) != NULL: the seed is read from it by the kernel (a
+ *   replayed graph draws new noise from a rewritten word) and `seed` is ignored.
+ * nsm_pert_loss_blocks: blocks of the forward for n elements (0: unsupported,
+ *   n <= 0 or n near 2^31).
+ * nsm_pert_loss_fwd: o, t and the P perturbed outputs pouts[0..P-1] hold n fp32
+ *   elements each; pouts is a HOST array of device pointers, copied into the
+ *   kernel's arguments (nothing is uploaded: the launch can be captured).
+ *   One pass reads each operand once; partial holds (1 + P) *
+ *   nsm_pert_loss_blocks(n) floats (per block the fp32 sums of |o - t| and of
+ *   each |o - p_i| in a fixed tree of 11 levels); a one-block finalize folds them
+ *   in double in a fixed order into the record out[3 + P]:
+ *     out[0] = l1 = mean|o - t|,  out[1] = pert = (1/P) sum_i mean|o - p_i|,
+ *     out[2] = alpha*l1 + (1 - alpha)*(vgg ? *vgg : 0) + w*pert,
+ *     out[3 + i] = mean|o - p_i|.   vgg: device scalar or NULL.
+ * nsm_pert_loss_bwd: one pass,
+ *     grad[e] (=|+=) g * (c0*sgn(o - t) + c1*sum_i sgn(o - p_i)),
+ *   c0 = alpha/n and c1 = w/(P*n) formed in double and rounded to fp32 once,
+ *   sgn(0) = 0, g = gscale ? *gscale : 1 (a device scalar as in
+ *   nsm_l1_loss_bwd); accumulate != 0 adds into grad. One writer per element. */
+#define NSM_PERT_MAX 8
+int nsm_perturb_variants(const float* x, const float* std, const float* noises, uint64_t seed,
+                         const int64_t* seed_dev, int P, int B, int C, int H, int W,
+                         float factor, float* out, void* stream);
+int nsm_pert_loss_blocks(int64_t n);
+int nsm_pert_loss_fwd(const float* o, const float* t, const float* const* pouts, int P, int64_t n,
+                      float alpha, float w, const float* vgg, float* partial, float* out,
+                      void* stream);
+int nsm_pert_loss_bwd(const float* o, const float* t, const float* const* pouts, int P, int64_t n,
+                      float alpha, float w, const float* gscale, float* grad, int accumulate,
+                      void* stream);
 
 /* ---- train-step tail (main.py:405,421: clip_grad_norm_ + AdamW) ----------- */
 int nsm_sumsq(const float* g, int64_t n, float* partial, float* out, void* stream);

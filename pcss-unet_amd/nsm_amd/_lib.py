@@ -143,6 +143,10 @@ _SIGS = {
     "nsm_stats_merge": (I, [P, I, I, I, P, P, P]),
     "nsm_channel_std": (I, [P, I, I, I, I, P, P, P]),
     "nsm_perturb": (I, [P, P, P, I, I, I, I, F, P, P]),
+    "nsm_perturb_variants": (I, [P, P, P, U64, P, I, I, I, I, I, F, P, P]),
+    "nsm_pert_loss_blocks": (I, [L]),
+    "nsm_pert_loss_fwd": (I, [P, P, P, I, L, F, F, P, P, P, P]),
+    "nsm_pert_loss_bwd": (I, [P, P, P, I, L, F, F, P, P, I, P]),
     "nsm_sumsq": (I, [P, L, P, P, P]),
     "nsm_clip_coef": (I, [P, F, F, P, P]),
     "nsm_adamw_step": (I, [P, P, P, P, L, F, F, F, F, F, I, P, P]),

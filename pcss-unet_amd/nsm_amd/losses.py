@@ -50,7 +50,11 @@
   checks it immediately (synchronising).
 * `PerturbationLoss(perturbation_count=3)`: pert_loss.py:7-90 — three
   no-grad forwards of the model on inputs perturbed by per-channel
-  std * 0.01 Gaussian noise, mean L1 to the original output.
+  std * 0.01 Gaussian noise, mean L1 to the original output. `noise="device"`
+  (opt-in; the default "torch" is that path unchanged) writes all variants
+  with one nsm_perturb_variants launch that draws the noise inside the kernel
+  (seeded from torch's CPU generator, or inside a graph capture from a device
+  word of torch's graph-safe generator: new noise every replay).
 * `EnhancedCustomLoss(device, alpha=0.9, perturb_weight=0.5)`: the wired
   perturbation-training loss of pert_loss.py:92-163 (§8f next-row #4). The
   reference's class cannot be constructed (it imports a `VGGLoss` that
@@ -63,6 +67,15 @@
   'high_freq_loss', 'penumbra_loss' and 'gradient_loss' (device scalars).
   `ssim_weight` / `ssim_data_range` as in CustomLoss: with the weight on the
   term joins `total` and the dict gains 'ssim_loss' = 1 - ssim (device scalar).
+  `fused=True` (opt-in; with `noise=`, `seed=`, `perturbation_count=` handed to
+  its PerturbationLoss): while training with a perturbation weight the L1 node
+  and the P perturbation nodes are ONE node on nsm_pert_loss_fwd/bwd; `total`
+  is the kernel's alpha*l1 + (1-alpha)*vgg + perturb_weight*pert, the parts in
+  the dict are detached views of its record (no 0-dim ATen arithmetic, no host
+  sync), and the perturbed forwards keep the main forward's prepared weight
+  layouts (unet.reuse_prepared_weights). `set_noises(t)` injects noises into
+  every following call. GraphedTrainStep takes the criterion as main.py:265
+  calls it ("The perturbation-loss step").
 * `measure_temporal_instability(frames, motion_vectors=None, alpha=5.0)`:
   pert_loss.py:166-199, mean over consecutive frame pairs of
   mean(exp(alpha*|f_t - f_{t-1}|) - 1) (`nsm_expdiff_mean`). With
@@ -72,6 +85,7 @@
   also has `temporal_instability_terms`, `reproject` and the streaming
   `TemporalInstability`; all four are re-exported here.
 """
+import ctypes
 import os
 import warnings
 
@@ -563,20 +577,139 @@ class CustomLoss(nn.Module):
             self._range.prepare(device)
 
 
+PERT_MAX = 8    # NSM_PERT_MAX (include/nsm.h): variants of one fused launch
+_NOISE_SOURCES = ("torch", "device")
+
+
+def _check_pert_options(what, perturbation_count, noise, fused=False):
+    if noise not in _NOISE_SOURCES:
+        raise ValueError(f"{what}: noise must be \"torch\" or \"device\", got {noise!r}")
+    if int(perturbation_count) != perturbation_count or perturbation_count < 1:
+        raise ValueError(f"{what}: perturbation_count must be a whole number >= 1, got "
+                         f"{perturbation_count!r}")
+    if (fused or noise == "device") and perturbation_count > PERT_MAX:
+        raise ValueError(f"{what}: the fused kernels take at most {PERT_MAX} variants, got "
+                         f"perturbation_count={perturbation_count}")
+
+
+def _check_noises(noises, count, shape):
+    """Injected noises: a list of `count` tensors shaped like the input, or one
+    [count, *shape] tensor. Host checks only."""
+    shape = tuple(shape)
+    if isinstance(noises, torch.Tensor):
+        if tuple(noises.shape) != (count,) + shape:
+            raise ValueError(f"perturbation noises: expected a {(count,) + shape} tensor, got "
+                             f"{tuple(noises.shape)}")
+        return
+    if len(noises) != count:
+        raise ValueError(f"perturbation noises: expected {count} tensors, got {len(noises)}")
+    for i, n in enumerate(noises):
+        if tuple(n.shape) != shape:
+            raise ValueError(f"perturbation noises: noise {i} has shape {tuple(n.shape)}, the "
+                             f"input {shape}")
+
+
+class _PertLossFn(torch.autograd.Function):
+    """alpha*L1(o, t) + (1-alpha)*vgg + w * mean_i L1(o, p_i) as ONE node on
+    nsm_pert_loss_fwd / nsm_pert_loss_bwd: one pass over o, t and the P
+    perturbed outputs each way. Returns (total, l1, pert): views of the
+    kernel's record, the last two detached. `vgg` is a detached device scalar
+    (its value joins `total`, no gradient) or None."""
+
+    @staticmethod
+    def forward(ctx, o, t, alpha, w, vgg, *pouts):
+        require_gpu(o, "perturbation-loss output")
+        o_ = o.detach().contiguous().to(torch.float32)
+        t_ = t.detach().contiguous().to(device=o.device, dtype=torch.float32)
+        ps = [p.detach().contiguous().to(device=o.device, dtype=torch.float32) for p in pouts]
+        n, P = o_.numel(), len(ps)
+        if t_.numel() != n or any(p.numel() != n for p in ps):
+            raise ValueError(f"perturbation loss: shape mismatch, output {tuple(o.shape)}, target "
+                             f"{tuple(t.shape)}, perturbed {[tuple(p.shape) for p in pouts]}")
+        nb = lib.nsm_pert_loss_blocks(n)
+        if nb <= 0 or not 1 <= P <= PERT_MAX:
+            raise ValueError(f"perturbation loss: {n} elements, {P} perturbed outputs")
+        partial = torch.empty((1 + P) * nb, dtype=torch.float32, device=o.device)
+        rec = torch.empty(3 + P, dtype=torch.float32, device=o.device)
+        v_ = None if vgg is None else vgg.detach().to(device=o.device, dtype=torch.float32)
+        ctx.table = (ctypes.c_void_p * P)(*[p.data_ptr() for p in ps])
+        call("nsm_pert_loss_fwd", ptr(o_), ptr(t_), ctx.table, P, n, float(alpha), float(w),
+             ptr(v_), ptr(partial), ptr(rec), stream())
+        ctx.save_for_backward(o_, t_, *ps)
+        ctx.alpha, ctx.w, ctx.oshape = float(alpha), float(w), o.shape
+        l1, pert = rec[0], rec[1]
+        ctx.mark_non_differentiable(l1, pert)
+        ctx.set_materialize_grads(False)
+        return rec[2], l1, pert
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        o_, t_, *ps = ctx.saved_tensors
+        grad = torch.empty_like(o_)
+        g_ = g.detach().contiguous().to(torch.float32)
+        call("nsm_pert_loss_bwd", ptr(o_), ptr(t_), ctx.table, len(ps), o_.numel(), ctx.alpha,
+             ctx.w, ptr(g_), ptr(grad), 0, stream())
+        return (grad.view(ctx.oshape),) + (None,) * (4 + len(ps))
+
+
 class PerturbationLoss(nn.Module):
-    def __init__(self, perturbation_count=3, alpha=0.9, std_factor=0.01):
+    """pert_loss.py:7-90. `noise` selects where the Gaussian noise comes from:
+    "torch" (default): one torch.randn_like and one nsm_perturb launch per
+    variant, the reference's random stream; "device": nsm_channel_std, then ONE
+    nsm_perturb_variants launch that writes all variants (views of one buffer)
+    and draws the noise inside the kernel from a counter-based generator. Its
+    seed is a host value from torch's CPU generator (so torch.manual_seed
+    reproduces it; `seed=<int>` gives the loss a generator of its own instead),
+    or, inside a graph capture, a device word from torch's graph-safe generator,
+    so every replay draws new noise. Injected `noises` (a list, or one
+    [P,B,C,H,W] tensor) go through the same kernel."""
+
+    def __init__(self, perturbation_count=3, alpha=0.9, std_factor=0.01, noise="torch", seed=None):
         super().__init__()
+        _check_pert_options("PerturbationLoss", perturbation_count, noise)
+        if seed is not None and noise != "device":
+            raise ValueError("PerturbationLoss: seed applies to noise=\"device\" only "
+                             "(noise=\"torch\" follows torch's generators)")
         self.perturbation_count = perturbation_count
         self.alpha = alpha
         self.std_factor = std_factor
+        self.noise = noise
+        self._gen = None if seed is None else torch.Generator().manual_seed(int(seed))
         self.loss_fn = L1Loss()
+
+    def _variants(self, x_, noises):
+        """noise="device": all variants from one nsm_perturb_variants launch."""
+        B, C, H, W = x_.shape
+        P = int(self.perturbation_count)
+        std = torch.empty(C, dtype=torch.float32, device=x_.device)
+        call("nsm_channel_std", ptr(x_), B, C, H, W, None, ptr(std), stream())
+        out = torch.empty((P,) + tuple(x_.shape), dtype=torch.float32, device=x_.device)
+        z, seed, seed_t = None, 0, None
+        if noises is not None:
+            if not isinstance(noises, torch.Tensor):
+                noises = torch.stack([n.to(device=x_.device, dtype=torch.float32)
+                                      for n in noises])
+            z = noises.to(device=x_.device, dtype=torch.float32).contiguous()
+        elif torch.cuda.is_current_stream_capturing():
+            # a captured step: the seed is device state, rewritten by every replay
+            seed_t = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=x_.device)
+        else:
+            seed = int(torch.randint(0, 2 ** 62, (1,), generator=self._gen).item())
+        call("nsm_perturb_variants", ptr(x_), ptr(std), ptr(z), seed, ptr(seed_t), P, B, C, H, W,
+             self.std_factor, ptr(out), stream())
+        return list(out.unbind(0))
 
     def perturb_input(self, x, noises=None):
         """Per-channel unbiased std over the batch, then x + n*std*0.01
-        (pert_loss.py:26-59); `noises` (list of tensors shaped like x) may be
-        supplied for parity, else drawn from torch.randn."""
+        (pert_loss.py:26-59); `noises` (list of tensors shaped like x, or one
+        stacked tensor) may be supplied for parity, else drawn from torch.randn
+        (noise="torch") or inside the kernel (noise="device")."""
+        if noises is not None:
+            _check_noises(noises, int(self.perturbation_count), x.shape)
         require_gpu(x, "perturbation input")
         x_ = x.detach().contiguous().to(torch.float32)
+        if self.noise == "device":
+            return self._variants(x_, noises)
         B, C, H, W = x_.shape
         std = torch.empty(C, dtype=torch.float32, device=x.device)
         call("nsm_channel_std", ptr(x_), B, C, H, W, None, ptr(std), stream())
@@ -603,8 +736,13 @@ class PerturbationLoss(nn.Module):
 class EnhancedCustomLoss(nn.Module):
     def __init__(self, device=None, alpha=0.9, perturb_weight=0.5, vgg=None, vgg_weights="auto",
                  vgg_grad=False, detail_weight=0.0, gradient_weight=0.0, ssim_weight=0.0,
-                 ssim_data_range=1.0):
+                 ssim_data_range=1.0, fused=False, noise="torch", seed=None,
+                 perturbation_count=3):
         super().__init__()
+        _check_pert_options("EnhancedCustomLoss", perturbation_count, noise, fused)
+        self.fused = bool(fused)
+        self._noises = None
+        self._zero = {}
         self.alpha = alpha
         self.perturb_weight = perturb_weight
         self.l1 = L1Loss()
@@ -617,7 +755,8 @@ class EnhancedCustomLoss(nn.Module):
                                detail_weight=detail_weight, gradient_weight=gradient_weight,
                                ssim_weight=ssim_weight, ssim_data_range=ssim_data_range)
         self.vgg_loss = getattr(self.base, "vgg_loss", None) or vgg
-        self.perturbation_loss = PerturbationLoss()
+        self.perturbation_loss = PerturbationLoss(perturbation_count=perturbation_count,
+                                                  noise=noise, seed=seed)
 
     def prepare_capture(self, device):
         self.base._range.prepare(device)
@@ -625,10 +764,70 @@ class EnhancedCustomLoss(nn.Module):
     def check_range_now(self):
         self.base._range.check()
 
+    def set_noises(self, noises):
+        """Use `noises` (a list of perturbation_count tensors shaped like the
+        input, or one [P,B,C,H,W] tensor) instead of drawn noise on every
+        following call, until set_noises(None). The tensors are read, never
+        copied, so a captured step (GraphedTrainStep) reads whatever they hold
+        at each replay. A parity hook, as `forward(..., noises=)`."""
+        if noises is not None:
+            P = int(self.perturbation_loss.perturbation_count)
+            first = noises[0] if len(noises) else None
+            if first is None:
+                raise ValueError(f"perturbation noises: expected {P} tensors, got 0")
+            _check_noises(noises, P, first.shape)
+        self._noises = noises
+
+    def _fused_forward(self, model, output, target, inputs, noises):
+        """fused=True while training with a perturbation weight: the L1 node and
+        the P perturbation nodes as one _PertLossFn; the other terms beside it."""
+        if self.vgg_grad:
+            from .vgg import _VggFn
+            vgg = _VggFn.apply(output, target, self.vgg_loss)
+        elif self.vgg_loss is not None:
+            vgg = torch.as_tensor(self.vgg_loss(output, target), device=output.device).detach()
+        else:
+            vgg = None
+        pins = self.perturbation_loss.perturb_input(inputs, noises)
+        # the weights are those of the forward that produced `output`: the
+        # perturbed forwards keep its prepared layouts (bitwise the same results)
+        from .unet import reuse_prepared_weights
+        with torch.no_grad(), reuse_prepared_weights(model):
+            pouts = [model(p) for p in pins]
+        # a differentiated VGG term stays its own node: its value joins below
+        total, l1, pert = _PertLossFn.apply(output, target, self.alpha, self.perturb_weight,
+                                            None if self.vgg_grad else vgg, *pouts)
+        if vgg is None:
+            vgg = self._zero.get(output.device)
+            if vgg is None:   # one fill per device, not one per step
+                vgg = self._zero[output.device] = torch.zeros((), device=output.device)
+        losses = {"l1_loss": l1, "vgg_loss": vgg.detach()}
+        if self.vgg_grad:
+            losses["vgg_loss"] = vgg
+            total = total + (1 - self.alpha) * vgg
+        if self.detail_weight != 0.0 or self.gradient_weight != 0.0:
+            d, hf, pen, sob = _DetailFn.apply(output, target, self.detail_weight,
+                                              self.detail_weight, self.gradient_weight)
+            total = total + d
+            losses.update(high_freq_loss=hf, penumbra_loss=pen, gradient_loss=sob)
+        if self.ssim_weight != 0.0:
+            s, term = _SsimFn.apply(output, target, self.ssim_weight, self.ssim_data_range)
+            total = total + s
+            losses["ssim_loss"] = term
+        losses["perturbation_loss"] = pert
+        losses["total_loss"] = total
+        return total, losses
+
     def forward(self, model, output, target, inputs, noises=None):
         # pert_loss.py:131: the same [0, 1] assertion, as CustomLoss's device flag
+        if noises is None:
+            noises = self._noises
+        if noises is not None and self.training and self.perturb_weight > 0:
+            _check_noises(noises, int(self.perturbation_loss.perturbation_count), inputs.shape)
         require_gpu(output, "EnhancedCustomLoss output")
         self.base._range.launch(output.detach().contiguous().to(torch.float32))
+        if self.fused and self.training and self.perturb_weight > 0:
+            return self._fused_forward(model, output, target, inputs, noises)
         l1 = l1_loss(output, target)
         if self.vgg_grad:
             # the same value, carrying d vgg / d output (autograd adds it to the

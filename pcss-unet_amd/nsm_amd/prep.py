@@ -160,6 +160,9 @@ class StepWeights:
         dev = mod.conv10.weight.device
         self.params = [p for p in mod.parameters()]
         self.ptrs = [p.data_ptr() for p in self.params]
+        # the parameters' version counters at the last run() of a forward
+        # (unet.reuse_prepared_weights skips a run that would rewrite the same)
+        self.stamp = None
         self.blocks = {}
         jobs, keep = [], []
         base = 0

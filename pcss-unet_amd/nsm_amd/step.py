@@ -13,6 +13,14 @@ What the graph holds fixed, and how the step stays the reference's:
     (`step(x, y)` does it);
   * Dropout2d masks: drawn from torch's graph-safe CUDA generator inside the
     graph (unet._masks_for -> nsm_dropout_masks_dev), new masks every replay;
+  * the perturbation criterion (a `loss_fn` with a `perturbation_loss`
+    attribute, EnhancedCustomLoss: main.py:265-271): called as
+    loss_fn(model, out, y, x), its perturbed forwards captured with the rest;
+    `step.losses` is the dict it returned, static device scalars rewritten by
+    every replay (a re-capture replaces them). Its noise is torch.randn_like on
+    the graph-safe generator (noise="torch") or drawn inside
+    nsm_perturb_variants from a device seed word (noise="device"): new noise
+    every replay either way;
   * the CustomLoss range assert: its sticky device flag only, allocated
     before the capture (`loss_fn.prepare_capture`); `loss_fn.check_range_now()`
     reads it, or the step itself every `range_check_every` replays;
@@ -56,6 +64,12 @@ class GraphedTrainStep:
                              "FlatAdam / FlatSGD), whose device tail keeps the optimizer step "
                              "count on the device")
         self.model, self.loss_fn, self.opt = model, loss_fn, optimizer
+        # main.py:265's own test: a criterion with a `perturbation_loss`
+        # (EnhancedCustomLoss) is called as loss_fn(model, out, y, x) and returns
+        # (total, parts); `losses` then holds the parts as static device scalars
+        # that every replay rewrites
+        self._pert = hasattr(loss_fn, "perturbation_loss")
+        self.losses = None
         self.loss_scale = float(loss_scale)
         # nsm_amd.GradScaler (default: the optimizer's): the backward is seeded
         # from the scaler's own scale word, which the captured tail updates, so
@@ -92,7 +106,12 @@ class GraphedTrainStep:
 
     def _body(self):
         out = self.model(self.x)
-        loss = self.loss_fn(out, self.y, self.x)
+        if self._pert:
+            # main.py:265-271: the perturbation criterion runs the model itself
+            loss, parts = self.loss_fn(self.model, out, self.y, self.x)
+            self.losses = {k: v.detach() for k, v in parts.items()}
+        else:
+            loss = self.loss_fn(out, self.y, self.x)
         # d(loss_scale * loss)/d loss seeded from a buffer filled before the
         # capture: the same gradient as (loss * s).backward(), without the
         # seed's fill (and the scale's multiply) launched by ATen in the graph

@@ -984,8 +984,43 @@ def _step_weights(mod, dtype, Rh, Rw, training, act_slots):
         return sw
     if fz is not None:
         fz.sws[key] = sw
+    stamp = tuple(p._version for p in sw.params)
+    if _REUSE is mod and sw.stamp == stamp:
+        # reuse_prepared_weights: the layouts in `sw` were written from these
+        # very parameter versions; only the forward's slots need zeroing
+        call("nsm_zero_u32", ptr(act_slots), act_slots.numel(), stream())
+        return sw
     sw.run(act_slots)
+    sw.stamp = stamp
     return sw
+
+
+_REUSE = None
+
+
+class reuse_prepared_weights:
+    """Forwards of `mod` inside this context skip the weight-preparation launch
+    when the layouts they would write are already there: the cached
+    StepWeights of the same signature was last run from parameters whose
+    version counters have not moved since (an optimizer step, a load or any
+    in-place write moves them, and the next forward prepares again). The
+    results are bitwise those of a forward that prepares: the launch is a pure
+    function of the parameters. EnhancedCustomLoss(fused=True) runs its
+    perturbed forwards in it: the four forwards of a step share one set of
+    weights."""
+
+    def __init__(self, mod):
+        self.mod = mod
+
+    def __enter__(self):
+        global _REUSE
+        self.prev, _REUSE = _REUSE, self.mod
+        return self
+
+    def __exit__(self, *exc):
+        global _REUSE
+        _REUSE = self.prev
+        return False
 
 
 class _UnetFn(torch.autograd.Function):
