@@ -737,6 +737,41 @@ int nsm_stats_blocks(int64_t hw);
 int nsm_stats_partial(const float* x, int B, int C, int64_t HW, double* records, void* stream);
 int nsm_stats_merge(const double* records, int B, int C, int per, double* frames, double* state,
                     void* stream);
+/* ---- image-error metrics of the validation pass (main.py:583-664, validate_direct;
+ * validate_consistency.py:119-120, MSE and PSNR) ------------------------------------
+ * Per image, over the pairs of an output o and a target t: a record of 6 doubles
+ *   {count, sum|d|, sum d^2, max|d|, nonfinite, out_of_range},  d = (double)o - (double)t.
+ * A pair in which either sample is non-finite is counted in `nonfinite` and left
+ * out of the other five; `out_of_range` counts the o of the remaining pairs outside
+ * [lo, hi]; a record without a finite pair is {0, 0, 0, 0, k, 0}. Records merge by
+ * adding in fp64 (the maximum by fmax) in a fixed order: the same call sequence
+ * gives the same bits. No atomics, no host synchronisation, no allocation.
+ * nsm_metrics_blocks: records per image of n elements (0: n < 1 or n >= 2^31).
+ * nsm_metrics_partial: o, t [B][n] fp32, contiguous, 4-byte aligned (no more is
+ *   assumed: ragged heads and tails of the 16-byte loads are handled inside);
+ *   one read of each; records [B * nsm_metrics_blocks(n)][6], block after block
+ *   of each image.
+ * nsm_metrics_merge: one launch. Folds records [B][per][6]: the `per` records of
+ *   an image in index order (runs of neighbours, then a fixed tree of
+ *   neighbouring runs) into the image's record (written to frames [B][6] unless
+ *   NULL), then the images in order into state [6], which the caller zeroes and
+ *   keeps across batches. With per = 1 and B = 1 it merges another accumulator's
+ *   state. acc (may be NULL; doubles [3 + K], zeroed by the caller) advances in
+ *   the same launch: acc[0] += 1 (batches); acc[1 + k] += *scalars[k] for the K <=
+ *   NSM_METRICS_SCALARS fp32 device scalars a criterion produced (scalars is a
+ *   HOST array of device pointers, copied into the kernel's arguments as
+ *   nsm_pert_loss_fwd's pouts: the launch can be captured); acc[1 + K] += the
+ *   batch's sum|d| / count (NaN without a finite pair); acc[2 + K] += B, the images
+ *   seen. log (with acc; NULL or log_capacity 0: none): image i of this batch is
+ *   also written to log[acc[2 + K] + i][6] (the count before the call) while that
+ *   index is below log_capacity. */
+#define NSM_METRICS_SCALARS 8
+int nsm_metrics_blocks(int64_t n);
+int nsm_metrics_partial(const float* o, const float* t, int B, int64_t n, float lo, float hi,
+                        double* records, void* stream);
+int nsm_metrics_merge(const double* records, int B, int per, const float* const* scalars, int K,
+                      double* frames, double* log, int64_t log_capacity, double* state,
+                      double* acc, void* stream);
 /* PerturbationLoss.perturb_input (pert_loss.py:26-59):
  * per-channel unbiased std over the batch of NCHW x -> std[C] */
 int nsm_channel_std(const float* x, int B, int C, int H, int W, float* partial, float* std,

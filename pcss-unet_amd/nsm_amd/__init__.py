@@ -22,6 +22,8 @@ from .sensitivity import (FeatureSensitivity, SensitivityResult,  # noqa: F401
 from .stats import (ChannelStats, StatsResult, channel_stats, dataset_stats,  # noqa: F401
                     save_stats, stats_json)
 from .step import GraphedTrainStep  # noqa: F401
+from .validation import (ImageMetrics, MetricsResult, ValidationResult,  # noqa: F401
+                         Validator, image_metrics, validate)
 from .vgg import MultiLayerVGGLoss  # noqa: F401
 
 __version__ = "0.1.0"

@@ -141,6 +141,9 @@ _SIGS = {
     "nsm_stats_blocks": (I, [L]),
     "nsm_stats_partial": (I, [P, I, I, L, P, P]),
     "nsm_stats_merge": (I, [P, I, I, I, P, P, P]),
+    "nsm_metrics_blocks": (I, [L]),
+    "nsm_metrics_partial": (I, [P, P, I, L, F, F, P, P]),
+    "nsm_metrics_merge": (I, [P, I, I, P, I, P, P, L, P, P, P]),
     "nsm_channel_std": (I, [P, I, I, I, I, P, P, P]),
     "nsm_perturb": (I, [P, P, P, I, I, I, I, F, P, P]),
     "nsm_perturb_variants": (I, [P, P, P, U64, P, I, I, I, I, I, F, P, P]),
