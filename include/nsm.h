@@ -890,7 +890,25 @@ int nsm_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr, floa
  *   Same launch count as nsm_grad_tail; no host sync, no atomics.
  * nsm_scaler_set: scaler_state[0] = scale (finite, > 0), [1] = tracker (>= 0);
  *   the other words keep their values (zero the buffer once before the first
- *   call). */
+ *   call).
+ *
+ * lr and max_norm as device words (opt-in): a hyper block is nsm_hyper_bytes()
+ * (16) bytes of device memory, 8-byte aligned: a double lr at byte 0, a float
+ * max_norm at byte 8, 4 bytes of padding. The *_dev entries take
+ * `const void* hyper` where their namesakes take lr (nsm_adamw_tail,
+ * nsm_adam_tail, nsm_sgd_tail) or max_norm (nsm_grad_tail,
+ * nsm_grad_tail_scaled) and read the value from the block: one uniform load
+ * per block before any other work, reads only, and then the namesake's
+ * arithmetic, so equal values give bitwise equal results (lr stays the double
+ * the Adam kernels use; the SGD kernel casts it to float as nsm_sgd_tail does
+ * on the host). stat[2] reports the max_norm read. A captured graph of them
+ * follows the block, so a schedule needs no new capture.
+ * nsm_hyper_set: block <- {lr, max_norm}, one thread, plain stores. The values
+ *   are arguments of that launch, so sets and (replayed) steps queued on one
+ *   stream with no host wait each see their own values. Checked before any
+ *   launch: lr finite and >= 0, max_norm >= 0 or +inf (no clipping), not NaN,
+ *   hyper non-NULL. Do not record it into the graph that holds the step: a
+ *   replay would write the recorded values back. */
 #define NSM_SCALER_WORDS 8
 int64_t nsm_tail_chunk(void);
 int nsm_tail_plan(const int64_t* seg_off, int nseg, int* blk_seg, int64_t* blk_lo,
@@ -920,6 +938,32 @@ int nsm_adam_tail(float* p, const float* g, float* m, float* v, const int* blk_s
 int nsm_sgd_tail(float* p, const float* g, float* buf, const int* blk_seg, const int64_t* blk_lo,
                  const int64_t* blk_hi, int nblk, const float* seg_coef, const int* flags,
                  const int* step, double lr, double momentum, double weight_decay, void* stream);
+size_t nsm_hyper_bytes(void);
+int nsm_hyper_set(void* hyper, double lr, float max_norm, void* stream);
+int nsm_grad_tail_dev(float* g, int nseg, const int64_t* seg_off, const int* seg_blk,
+                      const int* blk_seg, const int64_t* blk_lo, const int64_t* blk_hi, int nblk,
+                      float inv_world, float scale, const void* hyper, const float* noise,
+                      uint64_t seed, void* ws, size_t ws_bytes, float* seg_coef, float* stat,
+                      int* flags, int* step, void* stream);
+int nsm_grad_tail_scaled_dev(float* g, int nseg, const int64_t* seg_off, const int* seg_blk,
+                             const int* blk_seg, const int64_t* blk_lo, const int64_t* blk_hi,
+                             int nblk, float inv_world, void* scaler_state, const void* hyper,
+                             const float* noise, uint64_t seed, void* ws, size_t ws_bytes,
+                             float* seg_coef, float* stat, int* flags, int* step,
+                             float growth_factor, float backoff_factor, int growth_interval,
+                             int on_overflow, void* stream);
+int nsm_adamw_tail_dev(float* p, const float* g, float* m, float* v, const int* blk_seg,
+                       const int64_t* blk_lo, const int64_t* blk_hi, int nblk,
+                       const float* seg_coef, const int* flags, const int* step, const void* hyper,
+                       double beta1, double beta2, double eps, double weight_decay, void* stream);
+int nsm_adam_tail_dev(float* p, const float* g, float* m, float* v, const int* blk_seg,
+                      const int64_t* blk_lo, const int64_t* blk_hi, int nblk,
+                      const float* seg_coef, const int* flags, const int* step, const void* hyper,
+                      double beta1, double beta2, double eps, double weight_decay, void* stream);
+int nsm_sgd_tail_dev(float* p, const float* g, float* buf, const int* blk_seg,
+                     const int64_t* blk_lo, const int64_t* blk_hi, int nblk, const float* seg_coef,
+                     const int* flags, const int* step, const void* hyper, double momentum,
+                     double weight_decay, void* stream);
 
 /* ---- drop-in surface helpers ---------------------------------------------------
  * NCHW fp32 <-> NHWC [B*H*W][cp] (dtype NSM_F32 / NSM_BF16) for a standalone

@@ -289,11 +289,26 @@ struct TailScaler {
   int interval, on_overflow;
 };
 
-template <bool DYN>
+// The hyper block (nsm_hyper_set) holds the two hyper-parameters a schedule
+// moves, so a captured tail follows them without a new capture. lr is a double
+// because the Adam kernels form 1 - lr*wd and lr/bc1 in double from the double
+// the host holds; max_norm is the float this kernel takes (+inf: no clipping).
+// HDEV = false takes them as kernel arguments; HDEV = true reads them from the
+// block, one uniform load per block before any other work, and then runs the
+// same arithmetic: equal values give equal bits.
+struct TailHyper {
+  double lr;
+  float max_norm;
+  float pad;
+};
+static_assert(sizeof(TailHyper) == 16, "the hyper block is 16 bytes");
+
+template <bool DYN, bool HDEV>
 __global__ void __launch_bounds__(1024) tail_finalize_kernel(
     const int* __restrict__ seg_blk, int nseg, float scale, TailScaler sc, float max_norm,
-    TailWs w, float* __restrict__ seg_coef, float* __restrict__ stat, int* __restrict__ flags,
-    int* __restrict__ step) {
+    const TailHyper* __restrict__ hyper, TailWs w, float* __restrict__ seg_coef,
+    float* __restrict__ stat, int* __restrict__ flags, int* __restrict__ step) {
+  if (HDEV) max_norm = hyper->max_norm;
   // the pre-update scale, the same word in every thread (only thread 0 writes
   // the state, after the block's last barrier). The words the update rewrites
   // are read here too, so their latency hides behind the per-segment work
@@ -460,12 +475,15 @@ __global__ void __launch_bounds__(1024) tail_finalize_kernel(
 // ---- K5: AdamW (torch.optim.AdamW, single-tensor path) honouring the skip ----
 // p *= 1 - lr*wd; m = lerp(m, g, 1-b1); v = v*b2 + (1-b2)*g*g;
 // p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps); g = ((g*f1)*f2)*c (or 0 if zeroed)
+template <bool HDEV>
 __global__ void __launch_bounds__(TAIL_THREADS) tail_adamw_kernel(
     float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
     float* __restrict__ v, const int* __restrict__ blk_seg, const int64_t* __restrict__ blk_lo,
     const int64_t* __restrict__ blk_hi, const float* __restrict__ seg_coef,
-    const int* __restrict__ flags, const int* __restrict__ step, double lr, double beta1,
-    double beta2, float eps, double weight_decay) {
+    const int* __restrict__ flags, const int* __restrict__ step, double lr,
+    const TailHyper* __restrict__ hyper, double beta1, double beta2, float eps,
+    double weight_decay) {
+  if (HDEV) lr = hyper->lr;  // the block's double, then the argument path's arithmetic
   if (flags[0]) return;  // main.py:317/402/418 `continue`: no optimizer step
   const int b = blockIdx.x, sgi = blk_seg[b];
   const int64_t lo = blk_lo[b], hi = blk_hi[b];
@@ -496,12 +514,15 @@ __global__ void __launch_bounds__(TAIL_THREADS) tail_adamw_kernel(
 // g = ((g*f1)*f2)*c (or 0 if zeroed); g += wd*p; m = lerp(m, g, 1-b1);
 // v = v*b2 + (1-b2)*g*g; p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps).
 // 28 B per element, like AdamW: p, m, v read and written, g read.
+template <bool HDEV>
 __global__ void __launch_bounds__(TAIL_THREADS) tail_adam_kernel(
     float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
     float* __restrict__ v, const int* __restrict__ blk_seg, const int64_t* __restrict__ blk_lo,
     const int64_t* __restrict__ blk_hi, const float* __restrict__ seg_coef,
-    const int* __restrict__ flags, const int* __restrict__ step, double lr, double beta1,
-    double beta2, float eps, double weight_decay) {
+    const int* __restrict__ flags, const int* __restrict__ step, double lr,
+    const TailHyper* __restrict__ hyper, double beta1, double beta2, float eps,
+    double weight_decay) {
+  if (HDEV) lr = hyper->lr;  // the block's double, then the argument path's arithmetic
   if (flags[0]) return;  // skipped step
   const int b = blockIdx.x, sgi = blk_seg[b];
   const int64_t lo = blk_lo[b], hi = blk_hi[b];
@@ -536,13 +557,14 @@ __global__ void __launch_bounds__(TAIL_THREADS) tail_adam_kernel(
 // p -= lr*buf. 20 B per element (p read and written, buf read and written, g
 // read; the first step does not read buf). MOMENTUM = false is p -= lr*g with
 // no buffer at all: 12 B per element.
-template <bool MOMENTUM>
+template <bool MOMENTUM, bool HDEV>
 __global__ void __launch_bounds__(TAIL_THREADS) tail_sgd_kernel(
     float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
     const int* __restrict__ blk_seg, const int64_t* __restrict__ blk_lo,
     const int64_t* __restrict__ blk_hi, const float* __restrict__ seg_coef,
-    const int* __restrict__ flags, const int* __restrict__ step, float lr, float momentum,
-    float weight_decay) {
+    const int* __restrict__ flags, const int* __restrict__ step, float lr,
+    const TailHyper* __restrict__ hyper, float momentum, float weight_decay) {
+  if (HDEV) lr = (float)hyper->lr;  // the cast nsm_sgd_tail makes on the host
   if (flags[0]) return;  // skipped step
   const int b = blockIdx.x, sgi = blk_seg[b];
   const int64_t lo = blk_lo[b], hi = blk_hi[b];
@@ -594,12 +616,15 @@ extern "C" size_t nsm_tail_ws_bytes(int nseg, int nblk) {
   return tail_ws_layout(nseg, nblk, nullptr, nullptr);
 }
 
-// the launch sequence of both entries: sc.state == NULL is the static scale
+// the launch sequence of the four entries: sc.state == NULL is the static
+// scale; hyper != NULL reads max_norm from the hyper block (the argument is
+// then unused)
 static int grad_tail_launch(float* g, int nseg, const int64_t* seg_off, const int* seg_blk,
                             const int* blk_seg, const int64_t* blk_lo, const int64_t* blk_hi,
                             int nblk, float inv_world, float scale, TailScaler sc, float max_norm,
-                            const float* noise, uint64_t seed, void* ws, size_t ws_bytes,
-                            float* seg_coef, float* stat, int* flags, int* step, void* stream) {
+                            const TailHyper* hyper, const float* noise, uint64_t seed, void* ws,
+                            size_t ws_bytes, float* seg_coef, float* stat, int* flags, int* step,
+                            void* stream) {
   NSM_CHECK_ARG(g && seg_off && seg_blk && blk_seg && blk_lo && blk_hi && ws && seg_coef && stat &&
                     flags && step && nseg > 0 && nblk > 0,
                 "grad_tail: bad args");
@@ -615,14 +640,21 @@ static int grad_tail_launch(float* g, int nseg, const int64_t* seg_off, const in
   hipLaunchKernelGGL(tail_repair_kernel, dim3(nblk), dim3(TAIL_THREADS), 0, s, g, blk_seg, blk_lo,
                      blk_hi, noise, seed, step, w);
   NSM_LAUNCH_CHECK("tail_repair");
-  if (sc.state)
-    hipLaunchKernelGGL(tail_finalize_kernel<true>, dim3(1), dim3(1024), 0, s, seg_blk, nseg, scale,
-                       sc, max_norm, w, seg_coef, stat, flags, step);
-  else
-    hipLaunchKernelGGL(tail_finalize_kernel<false>, dim3(1), dim3(1024), 0, s, seg_blk, nseg,
-                       scale, sc, max_norm, w, seg_coef, stat, flags, step);
+  auto fin = sc.state ? (hyper ? tail_finalize_kernel<true, true> : tail_finalize_kernel<true, false>)
+                      : (hyper ? tail_finalize_kernel<false, true>
+                               : tail_finalize_kernel<false, false>);
+  hipLaunchKernelGGL(fin, dim3(1), dim3(1024), 0, s, seg_blk, nseg, scale, sc, max_norm, hyper, w,
+                     seg_coef, stat, flags, step);
   NSM_LAUNCH_CHECK("tail_finalize");
   return 0;
+}
+
+static const TailScaler kNoScaler{nullptr, 1.f, 1.f, 0, 0};
+
+static bool scaler_args_ok(const void* state, float growth, float backoff, int interval,
+                           int on_overflow) {
+  return state && growth > 1.f && backoff > 0.f && backoff < 1.f && interval > 0 &&
+         (on_overflow == 0 || on_overflow == 1);
 }
 
 extern "C" int nsm_grad_tail(float* g, int nseg, const int64_t* seg_off, const int* seg_blk,
@@ -632,8 +664,21 @@ extern "C" int nsm_grad_tail(float* g, int nseg, const int64_t* seg_off, const i
                              float* seg_coef, float* stat, int* flags, int* step, void* stream) {
   NSM_CHECK_ARG(scale > 0.f, "grad_tail: bad args");
   return grad_tail_launch(g, nseg, seg_off, seg_blk, blk_seg, blk_lo, blk_hi, nblk, inv_world,
-                          scale, TailScaler{nullptr, 1.f, 1.f, 0, 0}, max_norm, noise, seed, ws,
-                          ws_bytes, seg_coef, stat, flags, step, stream);
+                          scale, kNoScaler, max_norm, nullptr, noise, seed, ws, ws_bytes, seg_coef,
+                          stat, flags, step, stream);
+}
+
+extern "C" int nsm_grad_tail_dev(float* g, int nseg, const int64_t* seg_off, const int* seg_blk,
+                                 const int* blk_seg, const int64_t* blk_lo, const int64_t* blk_hi,
+                                 int nblk, float inv_world, float scale, const void* hyper,
+                                 const float* noise, uint64_t seed, void* ws, size_t ws_bytes,
+                                 float* seg_coef, float* stat, int* flags, int* step,
+                                 void* stream) {
+  NSM_CHECK_ARG(scale > 0.f, "grad_tail_dev: bad args");
+  NSM_CHECK_ARG(hyper, "grad_tail_dev: null hyper block");
+  return grad_tail_launch(g, nseg, seg_off, seg_blk, blk_seg, blk_lo, blk_hi, nblk, inv_world,
+                          scale, kNoScaler, 0.f, (const TailHyper*)hyper, noise, seed, ws, ws_bytes,
+                          seg_coef, stat, flags, step, stream);
 }
 
 extern "C" int nsm_grad_tail_scaled(float* g, int nseg, const int64_t* seg_off, const int* seg_blk,
@@ -644,14 +689,57 @@ extern "C" int nsm_grad_tail_scaled(float* g, int nseg, const int64_t* seg_off, 
                                     float* stat, int* flags, int* step, float growth_factor,
                                     float backoff_factor, int growth_interval, int on_overflow,
                                     void* stream) {
-  NSM_CHECK_ARG(scaler_state && growth_factor > 1.f && backoff_factor > 0.f &&
-                    backoff_factor < 1.f && growth_interval > 0 &&
-                    (on_overflow == 0 || on_overflow == 1),
+  NSM_CHECK_ARG(scaler_args_ok(scaler_state, growth_factor, backoff_factor, growth_interval,
+                               on_overflow),
                 "grad_tail_scaled: bad scaler args");
   return grad_tail_launch(g, nseg, seg_off, seg_blk, blk_seg, blk_lo, blk_hi, nblk, inv_world, 0.f,
                           TailScaler{(int*)scaler_state, growth_factor, backoff_factor,
                                      growth_interval, on_overflow},
-                          max_norm, noise, seed, ws, ws_bytes, seg_coef, stat, flags, step, stream);
+                          max_norm, nullptr, noise, seed, ws, ws_bytes, seg_coef, stat, flags, step,
+                          stream);
+}
+
+extern "C" int nsm_grad_tail_scaled_dev(float* g, int nseg, const int64_t* seg_off,
+                                        const int* seg_blk, const int* blk_seg,
+                                        const int64_t* blk_lo, const int64_t* blk_hi, int nblk,
+                                        float inv_world, void* scaler_state, const void* hyper,
+                                        const float* noise, uint64_t seed, void* ws,
+                                        size_t ws_bytes, float* seg_coef, float* stat, int* flags,
+                                        int* step, float growth_factor, float backoff_factor,
+                                        int growth_interval, int on_overflow, void* stream) {
+  NSM_CHECK_ARG(scaler_args_ok(scaler_state, growth_factor, backoff_factor, growth_interval,
+                               on_overflow),
+                "grad_tail_scaled_dev: bad scaler args");
+  NSM_CHECK_ARG(hyper, "grad_tail_scaled_dev: null hyper block");
+  return grad_tail_launch(g, nseg, seg_off, seg_blk, blk_seg, blk_lo, blk_hi, nblk, inv_world, 0.f,
+                          TailScaler{(int*)scaler_state, growth_factor, backoff_factor,
+                                     growth_interval, on_overflow},
+                          0.f, (const TailHyper*)hyper, noise, seed, ws, ws_bytes, seg_coef, stat,
+                          flags, step, stream);
+}
+
+// hyper block <- {lr, max_norm}. The two values are arguments of this launch,
+// not words of a host staging buffer: each queued set carries its own pair, so
+// sets and replays may alternate on a stream with no host wait between them.
+// One thread, plain stores.
+__global__ void hyper_set_kernel(TailHyper* hyper, double lr, float max_norm) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    hyper->lr = lr;
+    hyper->max_norm = max_norm;
+  }
+}
+
+extern "C" size_t nsm_hyper_bytes(void) { return sizeof(TailHyper); }
+
+extern "C" int nsm_hyper_set(void* hyper, double lr, float max_norm, void* stream) {
+  NSM_CHECK_ARG(lr >= 0.0 && lr <= DBL_MAX, "hyper_set: lr must be finite and >= 0 (got %g)", lr);
+  NSM_CHECK_ARG(max_norm >= 0.f, "hyper_set: max_norm must be >= 0 or +inf, not NaN (got %g)",
+                (double)max_norm);
+  NSM_CHECK_ARG(hyper, "hyper_set: null hyper block");
+  hipLaunchKernelGGL(hyper_set_kernel, dim3(1), dim3(64), 0, as_stream(stream), (TailHyper*)hyper,
+                     lr, max_norm);
+  NSM_LAUNCH_CHECK("hyper_set");
+  return 0;
 }
 
 // scaler state <- {scale, tracker}; the other words (found_inf, the two
@@ -672,19 +760,33 @@ extern "C" int nsm_scaler_set(void* scaler_state, float scale, int tracker, void
   return 0;
 }
 
+// Adam-type update launch of the four entries: hyper != NULL reads lr from the
+// hyper block (the argument is then unused)
+static int adam_family_launch(bool decoupled, const char* what, float* p, const float* g, float* m,
+                              float* v, const int* blk_seg, const int64_t* blk_lo,
+                              const int64_t* blk_hi, int nblk, const float* seg_coef,
+                              const int* flags, const int* step, double lr, const TailHyper* hyper,
+                              double beta1, double beta2, double eps, double weight_decay,
+                              void* stream) {
+  NSM_CHECK_ARG(p && g && m && v && blk_seg && blk_lo && blk_hi && seg_coef && flags && step &&
+                    nblk > 0,
+                "%s: bad args", what);
+  auto k = decoupled ? (hyper ? tail_adamw_kernel<true> : tail_adamw_kernel<false>)
+                     : (hyper ? tail_adam_kernel<true> : tail_adam_kernel<false>);
+  hipLaunchKernelGGL(k, dim3(nblk), dim3(TAIL_THREADS), 0, as_stream(stream), p, g, m, v, blk_seg,
+                     blk_lo, blk_hi, seg_coef, flags, step, lr, hyper, beta1, beta2, (float)eps,
+                     weight_decay);
+  NSM_LAUNCH_CHECK(what);
+  return 0;
+}
+
 extern "C" int nsm_adamw_tail(float* p, const float* g, float* m, float* v, const int* blk_seg,
                               const int64_t* blk_lo, const int64_t* blk_hi, int nblk,
                               const float* seg_coef, const int* flags, const int* step, double lr,
                               double beta1, double beta2, double eps, double weight_decay,
                               void* stream) {
-  NSM_CHECK_ARG(p && g && m && v && blk_seg && blk_lo && blk_hi && seg_coef && flags && step &&
-                    nblk > 0,
-                "adamw_tail: bad args");
-  hipLaunchKernelGGL(tail_adamw_kernel, dim3(nblk), dim3(TAIL_THREADS), 0, as_stream(stream), p, g,
-                     m, v, blk_seg, blk_lo, blk_hi, seg_coef, flags, step, lr, beta1, beta2,
-                     (float)eps, weight_decay);
-  NSM_LAUNCH_CHECK("adamw_tail");
-  return 0;
+  return adam_family_launch(true, "adamw_tail", p, g, m, v, blk_seg, blk_lo, blk_hi, nblk, seg_coef,
+                            flags, step, lr, nullptr, beta1, beta2, eps, weight_decay, stream);
 }
 
 extern "C" int nsm_adam_tail(float* p, const float* g, float* m, float* v, const int* blk_seg,
@@ -692,13 +794,46 @@ extern "C" int nsm_adam_tail(float* p, const float* g, float* m, float* v, const
                              const float* seg_coef, const int* flags, const int* step, double lr,
                              double beta1, double beta2, double eps, double weight_decay,
                              void* stream) {
-  NSM_CHECK_ARG(p && g && m && v && blk_seg && blk_lo && blk_hi && seg_coef && flags && step &&
-                    nblk > 0,
-                "adam_tail: bad args");
-  hipLaunchKernelGGL(tail_adam_kernel, dim3(nblk), dim3(TAIL_THREADS), 0, as_stream(stream), p, g,
-                     m, v, blk_seg, blk_lo, blk_hi, seg_coef, flags, step, lr, beta1, beta2,
-                     (float)eps, weight_decay);
-  NSM_LAUNCH_CHECK("adam_tail");
+  return adam_family_launch(false, "adam_tail", p, g, m, v, blk_seg, blk_lo, blk_hi, nblk, seg_coef,
+                            flags, step, lr, nullptr, beta1, beta2, eps, weight_decay, stream);
+}
+
+extern "C" int nsm_adamw_tail_dev(float* p, const float* g, float* m, float* v, const int* blk_seg,
+                                  const int64_t* blk_lo, const int64_t* blk_hi, int nblk,
+                                  const float* seg_coef, const int* flags, const int* step,
+                                  const void* hyper, double beta1, double beta2, double eps,
+                                  double weight_decay, void* stream) {
+  NSM_CHECK_ARG(hyper, "adamw_tail_dev: null hyper block");
+  return adam_family_launch(true, "adamw_tail_dev", p, g, m, v, blk_seg, blk_lo, blk_hi, nblk,
+                            seg_coef, flags, step, 0.0, (const TailHyper*)hyper, beta1, beta2, eps,
+                            weight_decay, stream);
+}
+
+extern "C" int nsm_adam_tail_dev(float* p, const float* g, float* m, float* v, const int* blk_seg,
+                                 const int64_t* blk_lo, const int64_t* blk_hi, int nblk,
+                                 const float* seg_coef, const int* flags, const int* step,
+                                 const void* hyper, double beta1, double beta2, double eps,
+                                 double weight_decay, void* stream) {
+  NSM_CHECK_ARG(hyper, "adam_tail_dev: null hyper block");
+  return adam_family_launch(false, "adam_tail_dev", p, g, m, v, blk_seg, blk_lo, blk_hi, nblk,
+                            seg_coef, flags, step, 0.0, (const TailHyper*)hyper, beta1, beta2, eps,
+                            weight_decay, stream);
+}
+
+static int sgd_launch(const char* what, float* p, const float* g, float* buf, const int* blk_seg,
+                      const int64_t* blk_lo, const int64_t* blk_hi, int nblk,
+                      const float* seg_coef, const int* flags, const int* step, double lr,
+                      const TailHyper* hyper, double momentum, double weight_decay, void* stream) {
+  NSM_CHECK_ARG(p && g && blk_seg && blk_lo && blk_hi && seg_coef && flags && step && nblk > 0 &&
+                    (buf || momentum == 0.0),
+                "%s: bad args", what);
+  const bool mom = momentum != 0.0;
+  auto k = mom ? (hyper ? tail_sgd_kernel<true, true> : tail_sgd_kernel<true, false>)
+               : (hyper ? tail_sgd_kernel<false, true> : tail_sgd_kernel<false, false>);
+  hipLaunchKernelGGL(k, dim3(nblk), dim3(TAIL_THREADS), 0, as_stream(stream), p, g,
+                     mom ? buf : (float*)nullptr, blk_seg, blk_lo, blk_hi, seg_coef, flags, step,
+                     (float)lr, hyper, mom ? (float)momentum : 0.f, (float)weight_decay);
+  NSM_LAUNCH_CHECK(what);
   return 0;
 }
 
@@ -706,17 +841,16 @@ extern "C" int nsm_sgd_tail(float* p, const float* g, float* buf, const int* blk
                             const int64_t* blk_lo, const int64_t* blk_hi, int nblk,
                             const float* seg_coef, const int* flags, const int* step, double lr,
                             double momentum, double weight_decay, void* stream) {
-  NSM_CHECK_ARG(p && g && blk_seg && blk_lo && blk_hi && seg_coef && flags && step && nblk > 0 &&
-                    (buf || momentum == 0.0),
-                "sgd_tail: bad args");
-  if (momentum != 0.0)
-    hipLaunchKernelGGL(tail_sgd_kernel<true>, dim3(nblk), dim3(TAIL_THREADS), 0, as_stream(stream),
-                       p, g, buf, blk_seg, blk_lo, blk_hi, seg_coef, flags, step, (float)lr,
-                       (float)momentum, (float)weight_decay);
-  else
-    hipLaunchKernelGGL(tail_sgd_kernel<false>, dim3(nblk), dim3(TAIL_THREADS), 0,
-                       as_stream(stream), p, g, (float*)nullptr, blk_seg, blk_lo, blk_hi, seg_coef,
-                       flags, step, (float)lr, 0.f, (float)weight_decay);
-  NSM_LAUNCH_CHECK("sgd_tail");
-  return 0;
+  return sgd_launch("sgd_tail", p, g, buf, blk_seg, blk_lo, blk_hi, nblk, seg_coef, flags, step,
+                    lr, nullptr, momentum, weight_decay, stream);
+}
+
+extern "C" int nsm_sgd_tail_dev(float* p, const float* g, float* buf, const int* blk_seg,
+                                const int64_t* blk_lo, const int64_t* blk_hi, int nblk,
+                                const float* seg_coef, const int* flags, const int* step,
+                                const void* hyper, double momentum, double weight_decay,
+                                void* stream) {
+  NSM_CHECK_ARG(hyper, "sgd_tail_dev: null hyper block");
+  return sgd_launch("sgd_tail_dev", p, g, buf, blk_seg, blk_lo, blk_hi, nblk, seg_coef, flags,
+                    step, 0.0, (const TailHyper*)hyper, momentum, weight_decay, stream);
 }

@@ -189,6 +189,15 @@ _SIGS = {
     "nsm_adamw_tail": (I, [P, P, P, P, P, P, P, I, P, P, P, D, D, D, D, D, P]),
     "nsm_adam_tail": (I, [P, P, P, P, P, P, P, I, P, P, P, D, D, D, D, D, P]),
     "nsm_sgd_tail": (I, [P, P, P, P, P, P, I, P, P, P, D, D, D, P]),
+    # lr / max_norm read from a device hyper block (P) where the namesake takes the value
+    "nsm_hyper_bytes": (Z, []),
+    "nsm_hyper_set": (I, [P, D, F, P]),
+    "nsm_grad_tail_dev": (I, [P, I, P, P, P, P, P, I, F, F, P, P, U64, P, Z, P, P, P, P, P]),
+    "nsm_grad_tail_scaled_dev": (I, [P, I, P, P, P, P, P, I, F, P, P, P, U64, P, Z, P, P, P, P, F,
+                                     F, I, I, P]),
+    "nsm_adamw_tail_dev": (I, [P, P, P, P, P, P, P, I, P, P, P, P, D, D, D, D, P]),
+    "nsm_adam_tail_dev": (I, [P, P, P, P, P, P, P, I, P, P, P, P, D, D, D, D, P]),
+    "nsm_sgd_tail_dev": (I, [P, P, P, P, P, P, I, P, P, P, P, D, D, P]),
     "nsm_nchw_to_nhwc": (I, [P, I, I, I, I, P, I, I, I, P]),
     "nsm_nhwc_to_nchw": (I, [P, I, I, I, I, I, P, I, P]),
     "nsm_range_flag": (I, [P, L, F, F, P, P]),

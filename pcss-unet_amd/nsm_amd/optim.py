@@ -38,6 +38,17 @@ argument of `nsm_grad_tail`) or an `nsm_amd.GradScaler` (`grad_scaler=`): then
 the tail is `nsm_grad_tail_scaled`, which reads the scale from the scaler's
 device state and applies torch.amp.GradScaler's update rule to it in the same
 finalize kernel (grad_scaler.py).
+
+lr and max_norm are kernel arguments too, unless the optimizer is built with
+`device_hyper=True` (sanitize=True only): then they live in a 16-byte device
+block (a double lr, a float max_norm) that the `*_dev` entries of the same
+kernels read, and `sync_hyper()` uploads the host group's lr and the current
+max_norm whenever they differ from the pair last uploaded (`nsm_hyper_set`, the
+values as arguments of a one-thread launch). `step()` calls it unless the
+stream is capturing; GraphedTrainStep calls it before each replay. So a
+LambdaLR / ReduceLROnPlateau / `set_epoch` / `load_state_dict` change reaches a
+captured step with no new capture. The host group's lr stays the truth:
+`state_dict()` is unchanged.
 """
 import math
 import os
@@ -164,8 +175,11 @@ class _FlatOptimizer(torch.optim.Optimizer):
     _REFUSED = {}
 
     def __init__(self, params, defaults, max_grad_norm=None, world_size=1, sanitize=False,
-                 grad_scale=1.0, seed=None, grad_scaler=None):
+                 grad_scale=1.0, seed=None, grad_scaler=None, device_hyper=False):
         params = list(params)
+        if device_hyper and not sanitize:
+            raise ValueError(f"{type(self).__name__}: device_hyper needs sanitize=True (the "
+                             "device tail is what reads lr and max_norm from the hyper block)")
         if grad_scaler is not None:
             if float(grad_scale) != 1.0:
                 raise ValueError(f"{type(self).__name__}: grad_scale is the static loss scale; "
@@ -211,6 +225,14 @@ class _FlatOptimizer(torch.optim.Optimizer):
         self.stat = torch.zeros(4, dtype=torch.float32, device=dev)
         if sanitize:
             self._plan(offs, dev)
+        # device_hyper: lr and max_norm live in a device block the tail reads
+        # (include/nsm.h, nsm_hyper_set), so a captured step follows a schedule
+        self.device_hyper = bool(device_hyper)
+        self._hyper_dev = None
+        self._hyper_sent = None      # the (lr, max_norm) pair last uploaded
+        if self.device_hyper:
+            self._hyper_dev = torch.zeros(int(lib.nsm_hyper_bytes()), dtype=torch.uint8,
+                                          device=dev)
         if seed is None:
             seed = int.from_bytes(os.urandom(8), "little") >> 1
             # data parallel: every rank must draw the same repair noise, or the
@@ -277,14 +299,52 @@ class _FlatOptimizer(torch.optim.Optimizer):
 
     def step_hyper(self):
         """The hyper-parameters a step passes as kernel arguments (a captured
-        graph freezes them: a change needs a new capture)."""
+        graph freezes them: a change needs a new capture). With device_hyper,
+        lr and max_norm are not among them: the tail reads them from the hyper
+        block, a constant of the step that sync_hyper() rewrites between steps
+        (so it is no part of step_state() either)."""
         g = self.param_groups[0]
+        keys = [k for k in self._hyper_keys() if not (self.device_hyper and k == "lr")]
         vals = tuple(tuple(g[k]) if isinstance(g[k], (tuple, list)) else float(g[k])
-                     for k in self._hyper_keys())
+                     for k in keys)
+        if not self.device_hyper:
+            vals += (self.max_grad_norm,)
         if self._scaler is not None:
             # the scale itself is device state: its changes need no new capture
-            return vals + (self.max_grad_norm, self._scaler.tail_args())
-        return vals + (self.max_grad_norm, self.grad_scale)
+            return vals + (self._scaler.tail_args(),)
+        return vals + (self.grad_scale,)
+
+    def _hyper_pair(self):
+        mx = float(self.max_grad_norm) if self.max_grad_norm is not None else float("inf")
+        return (float(self.param_groups[0]["lr"]), mx)
+
+    def sync_hyper(self):
+        """device_hyper: upload (lr, max_norm) to the hyper block if they differ
+        from the pair last uploaded (the first call always uploads): one
+        one-thread launch on the current stream, no host wait. The values are
+        arguments of that launch, so uploads and replays may be queued back to
+        back. On a capturing stream it raises: a recorded upload would write
+        the captured values back on every replay."""
+        if not self.device_hyper:
+            return
+        pair = self._hyper_pair()
+        if pair == self._hyper_sent:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{type(self).__name__}.sync_hyper: the stream is capturing; call "
+                               "it before the capture and before each replay")
+        with torch.cuda.device(self._hyper_dev.device):
+            call("nsm_hyper_set", ptr(self._hyper_dev), pair[0], pair[1], stream())
+        self._hyper_sent = pair
+
+    def hyper_values(self):
+        """device_hyper: {"lr", "max_norm"} as the hyper block holds them (host
+        sync; for inspection, like last_flags())."""
+        if not self.device_hyper:
+            raise RuntimeError(f"{type(self).__name__}: built without device_hyper=True")
+        raw = self._hyper_dev.cpu()
+        return {"lr": float(raw[:8].view(torch.float64)[0].item()),
+                "max_norm": float(raw[8:12].view(torch.float32)[0].item())}
 
     # main.py:357-358
     def set_epoch(self, epoch, num_epochs):
@@ -305,20 +365,30 @@ class _FlatOptimizer(torch.optim.Optimizer):
         n = self.flat.numel()
         st = stream()
         if self.sanitize:
-            mx = float(self.max_grad_norm) if self.max_grad_norm is not None else float("inf")
+            if self.device_hyper:
+                # the *_dev entries read max_norm (and lr) from the hyper block. A
+                # captured upload would write the frozen values back on every
+                # replay: under capture the block is the caller's to keep current
+                # (GraphedTrainStep, or sync_hyper() before graph.replay())
+                if not torch.cuda.is_current_stream_capturing():
+                    self.sync_hyper()
+                sfx, mx = "_dev", ptr(self._hyper_dev)
+            else:
+                sfx = ""
+                mx = float(self.max_grad_norm) if self.max_grad_norm is not None else float("inf")
             if self._scaler is not None:
-                call("nsm_grad_tail_scaled", ptr(g), self._nseg, ptr(self._seg_off),
+                call("nsm_grad_tail_scaled" + sfx, ptr(g), self._nseg, ptr(self._seg_off),
                      ptr(self._seg_blk), ptr(self._blk_seg), ptr(self._blk_lo), ptr(self._blk_hi),
                      self._nblk, self.inv_world, ptr(self._scaler.state_tensor()), mx, ptr(noise),
                      self.seed, ptr(self._ws), self._ws.numel(), ptr(self._seg_coef),
                      ptr(self.stat), ptr(self.flags), ptr(self._step_dev),
                      *self._scaler.tail_args(), st)
             else:
-                call("nsm_grad_tail", ptr(g), self._nseg, ptr(self._seg_off), ptr(self._seg_blk),
-                     ptr(self._blk_seg), ptr(self._blk_lo), ptr(self._blk_hi), self._nblk,
-                     self.inv_world, self.grad_scale, mx, ptr(noise), self.seed, ptr(self._ws),
-                     self._ws.numel(), ptr(self._seg_coef), ptr(self.stat), ptr(self.flags),
-                     ptr(self._step_dev), st)
+                call("nsm_grad_tail" + sfx, ptr(g), self._nseg, ptr(self._seg_off),
+                     ptr(self._seg_blk), ptr(self._blk_seg), ptr(self._blk_lo), ptr(self._blk_hi),
+                     self._nblk, self.inv_world, self.grad_scale, mx, ptr(noise), self.seed,
+                     ptr(self._ws), self._ws.numel(), ptr(self._seg_coef), ptr(self.stat),
+                     ptr(self.flags), ptr(self._step_dev), st)
             self._tail_update(g, grp, st)
             _bump(params)
             return None
@@ -398,9 +468,12 @@ class _FlatAdamFamily(_FlatOptimizer):
 
     def _tail_update(self, g, grp, st):
         b1, b2 = grp["betas"]
-        call(self._TAIL, ptr(self.flat), ptr(g), ptr(self.exp_avg), ptr(self.exp_avg_sq),
+        # device_hyper: the entry that reads lr from the hyper block
+        name, lr = (self._TAIL + "_dev", ptr(self._hyper_dev)) if self.device_hyper \
+            else (self._TAIL, float(grp["lr"]))
+        call(name, ptr(self.flat), ptr(g), ptr(self.exp_avg), ptr(self.exp_avg_sq),
              ptr(self._blk_seg), ptr(self._blk_lo), ptr(self._blk_hi), self._nblk,
-             ptr(self._seg_coef), ptr(self.flags), ptr(self._step_dev), float(grp["lr"]),
+             ptr(self._seg_coef), ptr(self.flags), ptr(self._step_dev), lr,
              float(b1), float(b2), float(grp["eps"]), float(grp["weight_decay"]), st)
 
     def _plain_update(self, g, n, grp, coef, st):
@@ -455,9 +528,10 @@ class FlatAdamW(_FlatAdamFamily):
 
     def __init__(self, params, lr=7e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-3,
                  max_grad_norm=None, world_size=1, sanitize=False, grad_scale=1.0, seed=None,
-                 grad_scaler=None):
+                 grad_scaler=None, device_hyper=False):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay),
-                         max_grad_norm, world_size, sanitize, grad_scale, seed, grad_scaler)
+                         max_grad_norm, world_size, sanitize, grad_scale, seed, grad_scaler,
+                         device_hyper)
 
 
 class FlatAdam(_FlatAdamFamily):
@@ -469,10 +543,11 @@ class FlatAdam(_FlatAdamFamily):
 
     def __init__(self, params, lr=7e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-4,
                  max_grad_norm=None, world_size=1, sanitize=False, grad_scale=1.0, seed=None,
-                 amsgrad=False, maximize=False, grad_scaler=None):
+                 amsgrad=False, maximize=False, grad_scaler=None, device_hyper=False):
         self._check_refused(dict(amsgrad=amsgrad, maximize=maximize))
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay),
-                         max_grad_norm, world_size, sanitize, grad_scale, seed, grad_scaler)
+                         max_grad_norm, world_size, sanitize, grad_scale, seed, grad_scaler,
+                         device_hyper)
 
 
 class FlatSGD(_FlatOptimizer):
@@ -492,12 +567,13 @@ class FlatSGD(_FlatOptimizer):
 
     def __init__(self, params, lr=7e-4, momentum=0.9, weight_decay=1e-4, max_grad_norm=None,
                  world_size=1, sanitize=False, grad_scale=1.0, seed=None, dampening=0,
-                 nesterov=False, maximize=False, grad_scaler=None):
+                 nesterov=False, maximize=False, grad_scaler=None, device_hyper=False):
         self._check_refused(dict(dampening=dampening, nesterov=nesterov, maximize=maximize))
         if momentum < 0:
             raise ValueError(f"FlatSGD: invalid momentum {momentum}")
         super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay),
-                         max_grad_norm, world_size, sanitize, grad_scale, seed, grad_scaler)
+                         max_grad_norm, world_size, sanitize, grad_scale, seed, grad_scaler,
+                         device_hyper)
 
     def _alloc_state(self):
         mu = self.param_groups[0]["momentum"]
@@ -518,9 +594,11 @@ class FlatSGD(_FlatOptimizer):
         return self.momentum_buffer if grp["momentum"] != 0 else None
 
     def _tail_update(self, g, grp, st):
-        call("nsm_sgd_tail", ptr(self.flat), ptr(g), ptr(self._buf(grp)), ptr(self._blk_seg),
+        name, lr = ("nsm_sgd_tail_dev", ptr(self._hyper_dev)) if self.device_hyper \
+            else ("nsm_sgd_tail", float(grp["lr"]))
+        call(name, ptr(self.flat), ptr(g), ptr(self._buf(grp)), ptr(self._blk_seg),
              ptr(self._blk_lo), ptr(self._blk_hi), self._nblk, ptr(self._seg_coef),
-             ptr(self.flags), ptr(self._step_dev), float(grp["lr"]), float(grp["momentum"]),
+             ptr(self.flags), ptr(self._step_dev), lr, float(grp["momentum"]),
              float(grp["weight_decay"]), st)
 
     def _plain_update(self, g, n, grp, coef, st):
@@ -574,7 +652,7 @@ def make_optimizer(params, optimizer_type, lr, **kw):
     AdamW(weight_decay=1e-3), anything else -> SGD(momentum=0.9,
     weight_decay=1e-4), on the flat-buffer optimizers. The comparison is the
     reference's (exact, case-sensitive); `kw` takes max_grad_norm, world_size,
-    sanitize, grad_scale, seed and grad_scaler."""
+    sanitize, grad_scale, seed, grad_scaler and device_hyper."""
     if optimizer_type == 'adam':
         return FlatAdam(params, lr=lr, weight_decay=1e-4, **kw)
     elif optimizer_type == 'adamw':

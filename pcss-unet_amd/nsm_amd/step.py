@@ -26,10 +26,15 @@ What the graph holds fixed, and how the step stays the reference's:
     reads it, or the step itself every `range_check_every` replays;
   * version counters: each replay bumps those of the parameters and buffers
     (the kernels rewrote them), so infer.GraphedUnet refreshes its layouts;
-  * hyper-parameters passed as kernel arguments (lr, betas or momentum, eps,
-    weight decay, max_norm, the static loss scale): the step re-captures when
-    one of them changes (an epoch's LambdaLR / max_norm schedule costs one
-    capture); a `nsm_amd.GradScaler`'s scale is device state instead, read by
+  * hyper-parameters passed as kernel arguments (betas or momentum, eps,
+    weight decay, the static loss scale, and by default lr and max_norm): the
+    step re-captures when one of them changes, so on the default path an
+    epoch's LambdaLR / max_norm schedule costs one capture. An optimizer built
+    with `device_hyper=True` keeps lr and max_norm in a device block the tail
+    reads: the step uploads a changed pair before the replay
+    (`opt.sync_hyper()`, at most one one-thread launch, none when nothing
+    changed) and never re-captures for them; `step.captures` counts the
+    captures made. A `nsm_amd.GradScaler`'s scale is device state too, read by
     the backward's seed and the tail and updated by the tail inside the graph,
     so it moves without a capture;
   * parameter / buffer addresses: FlatAdamW's flat storage keeps them; a
@@ -93,6 +98,7 @@ class GraphedTrainStep:
         # only when the caller runs loss_fn.check_range_now()
         self.range_check_every = int(range_check_every)
         self.replays = 0
+        self.captures = 0       # captures made so far (1 after construction)
         self.graph = None
         self._capture()
 
@@ -132,6 +138,12 @@ class GraphedTrainStep:
 
     def _capture(self, warmup=None):
         warmup = self.warmup if warmup is None else warmup
+        # a device_hyper optimizer: the hyper block is current before the capture
+        # begins (inside it step() uploads nothing: a recorded upload would
+        # write today's lr and max_norm back on every replay)
+        sync_hyper = getattr(self.opt, "sync_hyper", None)
+        if sync_hyper is not None:
+            sync_hyper()
         if self._scaler is not None:
             # the scale word itself (opt.step_state() holds the scaler's state, so
             # the warm-up steps' backoffs and growths are undone below)
@@ -162,11 +174,14 @@ class GraphedTrainStep:
                 t.copy_(v)
         self._hyp = self._hyper()
         self._ptrs = self._addresses()
+        self.captures += 1
 
     def __call__(self, x=None, y=None):
         """One step: copy the batch in (if given), replay; returns the loss
-        tensor (device, unscaled). The first call after a hyper-parameter
-        change re-captures first (no eager steps: the caches are warm)."""
+        tensor (device, unscaled). The first call after a change of a
+        hyper-parameter that is a kernel argument re-captures first (no eager
+        steps: the caches are warm); a device_hyper optimizer's lr and max_norm
+        are uploaded instead."""
         if x is not None:
             self.x.detach().copy_(x)
         if y is not None:
@@ -177,6 +192,9 @@ class GraphedTrainStep:
         if self._hyper() != self._hyp:
             self.graph = None
             self._capture(warmup=0)   # the caches are warm
+        sync_hyper = getattr(self.opt, "sync_hyper", None)
+        if sync_hyper is not None:
+            sync_hyper()              # lr / max_norm of a device_hyper optimizer
         self.graph.replay()
         # the replay rewrote the parameters and the BN buffers with HIP kernels;
         # the Python-side version bumps (FlatAdamW's, the forward's BN one) ran
