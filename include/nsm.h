@@ -304,6 +304,15 @@ int nsm_conv3x3_wgrad_wino_h2(const void* dMh, const void* Vh, int B, int H, int
 int nsm_wino_gemm_h2(const void* V, const void* U, int B, int H, int W, int cin_p, int cout_p,
                      int tile, float* Mb, const uint32_t* amax_v, float beta_v,
                      const uint32_t* amax_u, float beta_u, void* stream);
+/* The decisions of the two h2 Winograd GEMMs on this device, from the function
+ * their launches use (host int arrays): nsm_wino_gemm_h2_plan -> plan[0] = the
+ * tile nsm_wino_gemm_h2 runs (1: 256x256, 2: 256x128, 3: 128x128, 4: 256x64,
+ * 5: 128x32 rows x channels), plan[1] = the kernel form (0: gemm_h2, 1:
+ * gemm_h2q, 2: the persistent gemm_h2p); nsm_wino_wgrad_h2_plan -> {BM, BN,
+ * splits, kchunk} of nsm_conv3x3_wgrad_wino_h2 (BM x BN = cout x cin tile,
+ * splits K slabs of kchunk Winograd tiles each, the last one shorter). */
+int nsm_wino_gemm_h2_plan(int B, int H, int W, int cin_p, int cout_p, int tile, int* plan);
+int nsm_wino_wgrad_h2_plan(int B, int H, int W, int cin_p, int cout_p, int tile, int* plan);
 /* ---- the DoubleConv's 1x1 convolution on h2 operands (csrc/nsm_conv_h2d.inc)
  * Replaces nn.Conv2d(in, out, 1) (Unetmodel.py:26), its input gradient with
  * the first BN's backward fused (as nsm_conv1x1_dgrad_bnbwd) and its weight

@@ -80,6 +80,20 @@ extern "C" size_t nsm_wino_wgrad_h2_ws(int B, int H, int W, int cin_p, int cout_
   return plan_wino_wgrad_h2(g.T, cin_p, cout_p, g.alpha2).slab_floats;
 }
 
+extern "C" int nsm_wino_wgrad_h2_plan(int B, int H, int W, int cin_p, int cout_p, int tile,
+                                      int* plan) {
+  WinoGeom g;
+  NSM_CHECK_ARG(plan && wino_geom(tile, B, H, W, g) && cin_p > 0 && cout_p > 0 && cin_p % 32 == 0 &&
+                    cout_p % 32 == 0,
+                "wino_wgrad_h2_plan: bad args");
+  const WinoWgradPlan p = plan_wino_wgrad_h2(g.T, cin_p, cout_p, g.alpha2);
+  plan[0] = p.BM;
+  plan[1] = p.BN;
+  plan[2] = p.splits;
+  plan[3] = p.kchunk;
+  return 0;
+}
+
 extern "C" int nsm_conv3x3_wgrad_wino_h2(const void* dMh, const void* Vh, int B, int H, int W,
                                          int cin_p, int cout_p, int cin, int cout, int tile,
                                          float* dw, float* ws, size_t ws_floats,
@@ -132,6 +146,18 @@ extern "C" int nsm_wino_gemm_h2(const void* V, const void* U, int B, int H, int 
                 "wino_gemm_h2: operand too large");
   return wino_gemm_h2((const bf16_t*)V, (const bf16_t*)U, g.T, cin_p, cout_p, g.alpha2, Mb,
                       H2Scale{amax_v, beta_v}, H2Scale{amax_u, beta_u}, as_stream(stream));
+}
+
+extern "C" int nsm_wino_gemm_h2_plan(int B, int H, int W, int cin_p, int cout_p, int tile,
+                                     int* plan) {
+  WinoGeom g;
+  NSM_CHECK_ARG(plan && wino_geom(tile, B, H, W, g) && cin_p > 0 && cout_p > 0 && cin_p % 32 == 0 &&
+                    cout_p % 32 == 0,
+                "wino_gemm_h2_plan: bad args");
+  const WinoGemmH2Plan p = plan_wino_gemm_h2(g.T, cin_p, cout_p, g.alpha2);
+  plan[0] = p.tile;
+  plan[1] = p.form;
+  return 0;
 }
 
 // the weight-gradient plan of the f16 path: the h2 plan's, on its 256 / 128 tiles

@@ -1070,20 +1070,30 @@ static bool h2p_nfast() { static const bool v = env_flag("NSM_H2P_NFAST", true);
 // persistent grid (gemm_h2p_kernel)
 static bool h2_persist() { static const bool v = env_flag("NSM_H2_PERSIST", true); return v; }
 
+// whether a 256-row GEMM of `total` tiles over K f16 columns runs on the
+// persistent grid (gemm_h2p_kernel) rather than one tile per block
+static bool h2_persistent(long long total, int K) {
+  return h2_persist() && K % 128 == 0 && total > cu_count() && total < (1ll << 30);
+}
+
+template <int BM, int BN, int WM, int WN, class AL, class BL, bool SP = false, bool O16 = false>
+static int launch_h2p(dim3 grid, hipStream_t s, const typename AL::P& ap, const typename BL::P& bp,
+                      const EpiH2P& ep, int M, int N, int K, H2Scale sa, H2Scale sb) {
+  constexpr int NT = WM * WN * 64;
+  const long long total = (long long)grid.x * grid.y * grid.z;
+  hipLaunchKernelGGL((gemm_h2p_kernel<BM, BN, WM, WN, AL, BL, SP, O16>), dim3(cu_count()), dim3(NT), 0, s,
+                     ap, bp, ep, M, N, K, (int)grid.x, (int)grid.y, (int)total, sa, sb,
+                     h2p_nfast() ? 1 : 0);
+  NSM_LAUNCH_CHECK("gemm_h2p");
+  return 0;
+}
+
 template <int BM, int BN, int WM, int WN, class AL, class BL, bool SP = false, bool O16 = false>
 static int launch_h2q_or_p(dim3 grid, hipStream_t s, const typename AL::P& ap,
                            const typename BL::P& bp, const EpiH2P& ep, int M, int N, int K,
                            H2Scale sa, H2Scale sb) {
-  const long long total = (long long)grid.x * grid.y * grid.z;
-  const int cus = cu_count();
-  if (h2_persist() && K % 128 == 0 && total > cus && total < (1ll << 30)) {
-    constexpr int NT = WM * WN * 64;
-    hipLaunchKernelGGL((gemm_h2p_kernel<BM, BN, WM, WN, AL, BL, SP, O16>), dim3(cus), dim3(NT), 0, s, ap,
-                       bp, ep, M, N, K, (int)grid.x, (int)grid.y, (int)total, sa, sb,
-                       h2p_nfast() ? 1 : 0);
-    NSM_LAUNCH_CHECK("gemm_h2p");
-    return 0;
-  }
+  if (h2_persistent((long long)grid.x * grid.y * grid.z, K))
+    return launch_h2p<BM, BN, WM, WN, AL, BL, SP, O16>(grid, s, ap, bp, ep, M, N, K, sa, sb);
   return launch_h2q<BM, BN, WM, WN, AL, BL, SP, O16>(grid, s, ap, bp, ep, M, N, K, sa, sb);
 }
 
@@ -1115,13 +1125,16 @@ int nsm::wino_gemm_f16(const bf16_t* V, const bf16_t* U, long long T, int cin_p,
              : launch_h2q_or_p<256, 128, 4, 2, R256, R128, true>(g128, s, ap, bp, ep, M, N, K, sv, su);
 }
 
-// batched M = T x N = cout GEMMs over K = cin channels (2 cin f16 columns)
-static int wino_gemm_h2(const bf16_t* V, const bf16_t* U, long long T, int cin_p, int cout_p,
-                        int nb, float* Mb, H2Scale sv, H2Scale su, hipStream_t s) {
+// The forward / dgrad GEMM's decision, shared by the launch below and the
+// query entry nsm_wino_gemm_h2_plan: tile 1 = 256x256, 2 = 256x128, 3 = 128x128,
+// 4 = 256x64, 5 = 128x32 (a forced tile that cout_p does not divide falls to the
+// next one that fits); form 0 = gemm_h2_kernel, 1 = gemm_h2q_kernel, 2 =
+// gemm_h2p_kernel (the 256-row tiles only)
+struct WinoGemmH2Plan {
+  int tile, form;
+};
+static WinoGemmH2Plan plan_wino_gemm_h2(long long T, int cin_p, int cout_p, int nb) {
   const int M = (int)T, N = cout_p, K = 2 * cin_p;
-  H2RowsP ap{V, 2 * cin_p, M, (long long)T * 2 * cin_p};
-  H2RowsP bp{U, 2 * cin_p, N, (long long)cout_p * 2 * cin_p};
-  EpiH2P ep{Mb, cout_p, (long long)T * cout_p};
   int tile = h2_tile_env();
   if (!tile) {
     if (N % 256 == 0 && (long long)ceil_div(M, 256) * (N / 256) * nb >= 768) tile = 1;
@@ -1129,37 +1142,49 @@ static int wino_gemm_h2(const bf16_t* V, const bf16_t* U, long long T, int cin_p
     else if (N % 128 == 0) tile = 3;
     else tile = N % 64 == 0 ? 4 : 5;
   }
-  switch (tile) {
-    case 1:
-      if (N % 256 == 0) {
-        const dim3 g(ceil_div(M, 256), N / 256, nb);
-        if (h2_mf16())
-          return launch_h2q_or_p<256, 256, 2, 4, H2RowsDma<256, 8>, H2RowsDma<256, 8>>(
-              g, s, ap, bp, ep, M, N, K, sv, su);
-        return launch_h2<256, 256, 2, 4, H2RowsDma<256, 8>, H2RowsDma<256, 8>>(g, s, ap, bp, ep, M, N,
-                                                                             K, K, 1, sv, su);
-      }
-      [[fallthrough]];
-    case 2:
-      if (N % 128 == 0) {
-        const dim3 g(ceil_div(M, 256), N / 128, nb);
-        if (h2_mf16())
-          return launch_h2q_or_p<256, 128, 4, 2, H2RowsDma<256, 8>, H2RowsDma<128, 8>>(
-              g, s, ap, bp, ep, M, N, K, sv, su);
-        return launch_h2<256, 128, 4, 2, H2RowsDma<256, 8>, H2RowsDma<128, 8>>(g, s, ap, bp, ep, M, N,
-                                                                             K, K, 1, sv, su);
-      }
-      [[fallthrough]];
+  if (tile < 1 || tile > 5) tile = 5;
+  if (tile == 1 && N % 256) tile = 2;
+  if (tile == 2 && N % 128) tile = 3;
+  if (tile == 3 && N % 128) tile = 4;
+  if (tile == 4 && N % 64) tile = 5;
+  int form = 0;
+  if (tile <= 2 && h2_mf16()) {
+    const long long total = (long long)ceil_div(M, 256) * (N / (tile == 1 ? 256 : 128)) * nb;
+    form = h2_persistent(total, K) ? 2 : 1;
+  }
+  return WinoGemmH2Plan{tile, form};
+}
+
+// batched M = T x N = cout GEMMs over K = cin channels (2 cin f16 columns)
+static int wino_gemm_h2(const bf16_t* V, const bf16_t* U, long long T, int cin_p, int cout_p,
+                        int nb, float* Mb, H2Scale sv, H2Scale su, hipStream_t s) {
+  const int M = (int)T, N = cout_p, K = 2 * cin_p;
+  H2RowsP ap{V, 2 * cin_p, M, (long long)T * 2 * cin_p};
+  H2RowsP bp{U, 2 * cin_p, N, (long long)cout_p * 2 * cin_p};
+  EpiH2P ep{Mb, cout_p, (long long)T * cout_p};
+  const WinoGemmH2Plan pl = plan_wino_gemm_h2(T, cin_p, cout_p, nb);
+  switch (pl.tile) {
+    case 1: {
+      const dim3 g(ceil_div(M, 256), N / 256, nb);
+      using R = H2RowsDma<256, 8>;
+      if (pl.form == 2) return launch_h2p<256, 256, 2, 4, R, R>(g, s, ap, bp, ep, M, N, K, sv, su);
+      if (pl.form == 1) return launch_h2q<256, 256, 2, 4, R, R>(g, s, ap, bp, ep, M, N, K, sv, su);
+      return launch_h2<256, 256, 2, 4, R, R>(g, s, ap, bp, ep, M, N, K, K, 1, sv, su);
+    }
+    case 2: {
+      const dim3 g(ceil_div(M, 256), N / 128, nb);
+      using RA = H2RowsDma<256, 8>;
+      using RB = H2RowsDma<128, 8>;
+      if (pl.form == 2) return launch_h2p<256, 128, 4, 2, RA, RB>(g, s, ap, bp, ep, M, N, K, sv, su);
+      if (pl.form == 1) return launch_h2q<256, 128, 4, 2, RA, RB>(g, s, ap, bp, ep, M, N, K, sv, su);
+      return launch_h2<256, 128, 4, 2, RA, RB>(g, s, ap, bp, ep, M, N, K, K, 1, sv, su);
+    }
     case 3:
-      if (N % 128 == 0)
-        return launch_h2<128, 128, 2, 2, H2RowsDma<128, 4>, H2RowsDma<128, 4>>(
-            dim3(ceil_div(M, 128), N / 128, nb), s, ap, bp, ep, M, N, K, K, 1, sv, su);
-      [[fallthrough]];
+      return launch_h2<128, 128, 2, 2, H2RowsDma<128, 4>, H2RowsDma<128, 4>>(
+          dim3(ceil_div(M, 128), N / 128, nb), s, ap, bp, ep, M, N, K, K, 1, sv, su);
     case 4:
-      if (N % 64 == 0)
-        return launch_h2<256, 64, 4, 1, H2RowsDma<256, 4>, H2RowsDma<64, 4>>(
-            dim3(ceil_div(M, 256), N / 64, nb), s, ap, bp, ep, M, N, K, K, 1, sv, su);
-      [[fallthrough]];
+      return launch_h2<256, 64, 4, 1, H2RowsDma<256, 4>, H2RowsDma<64, 4>>(
+          dim3(ceil_div(M, 256), N / 64, nb), s, ap, bp, ep, M, N, K, K, 1, sv, su);
     default:
       return launch_h2<128, 32, 4, 1, H2RowsDma<128, 4>, H2RowsDma<32, 4>>(
           dim3(ceil_div(M, 128), ceil_div(N, 32), nb), s, ap, bp, ep, M, N, K, K, 1, sv, su);

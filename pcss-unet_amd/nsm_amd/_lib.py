@@ -41,6 +41,8 @@ _SIGS = {
     "nsm_pmc_calib": (I, [I, P, P, L, P]),
     "nsm_to_h2": (I, [P, L, I, P, F, P, P]),
     "nsm_wino_gemm_h2": (I, [P, P, I, I, I, I, I, I, P, P, F, P, F, P]),
+    "nsm_wino_gemm_h2_plan": (I, [I, I, I, I, I, I, P]),
+    "nsm_wino_wgrad_h2_plan": (I, [I, I, I, I, I, I, P]),
     "nsm_wino_beta": (F, [I, I]),
     "nsm_wino_input_h2": (I, [P, I, I, I, I, I, I, I, I, P, P, P]),
     "nsm_wino_dual_input_h2": (I, [P, I, I, I, I, I, I, P, P, P, P]),

@@ -469,6 +469,27 @@ def wino_beta(tile, which):
     return _BETA[key]
 
 
+H2_GEMM_FORMS = ("gemm_h2", "gemm_h2q", "gemm_h2p")
+
+
+def wino_gemm_h2_plan(B, H, W, cin_p, cout_p, tile):
+    """(tile 1..5, kernel form) nsm_wino_gemm_h2 runs for this shape on this
+    device (nsm_wino_gemm_h2_plan)."""
+    import ctypes
+    plan = (ctypes.c_int * 2)()
+    call("nsm_wino_gemm_h2_plan", B, H, W, cin_p, cout_p, tile, plan)
+    return plan[0], H2_GEMM_FORMS[plan[1]]
+
+
+def wino_wgrad_h2_plan(B, H, W, cin_p, cout_p, tile):
+    """(BM, BN, splits, kchunk) of nsm_conv3x3_wgrad_wino_h2 for this shape
+    (nsm_wino_wgrad_h2_plan)."""
+    import ctypes
+    plan = (ctypes.c_int * 4)()
+    call("nsm_wino_wgrad_h2_plan", B, H, W, cin_p, cout_p, tile, plan)
+    return tuple(plan)
+
+
 def wino_dual_input_h2(dy, B, H, W, tile, amax_dy):
     """wino_dual_input writing (Vd, dM) as h2 tensors; amax_dy: max|dy| slot
     (filled by dy's producer), their scale source."""
