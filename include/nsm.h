@@ -337,6 +337,25 @@ int nsm_conv1x1_dgrad_bnbwd_h2(const void* dy2h, int M, int cop, const void* w2d
                                float* out, int ldo, const uint32_t* amax_dy2,
                                const uint32_t* amax_w, uint32_t* amax_out, uint32_t* amax_k1dz,
                                void* stream);
+/* The kernel form of nsm_conv1x1_dgrad_bnbwd_h2 (csrc/nsm_conv_h2d.inc): one
+ * output tile per block, or a persistent grid that walks the tiles with the
+ * K-tile stream and the Y1 fetch running across them (same tile, same
+ * arithmetic: bitwise the same results). nsm_set_h2d_bnb_persist: form 0 =
+ * policy (default; env NSM_H2D_BNB_PERSIST=1), 1 = one tile per block
+ * everywhere (env 0), 2 = persistent wherever the form covers the shape (env
+ * 2), < 0 = unchanged; grid = blocks of the persistent form, 0 = as many as
+ * are resident at once, < 0 = unchanged; prev (may be NULL) receives the
+ * previous {form, grid}. Host-wide, not per stream.
+ * nsm_conv1x1_dgrad_bnbwd_h2_plan: plan[0] = tile (2: 256x128, 3: 128x128, 4:
+ * 256x64, 5: 128x64, 6: 128x32), plan[1] = 0 one tile per block / 1
+ * persistent, plan[2] = the persistent grid (0 for form 0), plan[3] = rows
+ * per partial row (= nsm_conv1x1_h2_rows). nsm_h2d_tile_walk: the (M block, N
+ * block, logical index) triples that block `block` of a persistent grid of
+ * `grid` blocks visits over gx x gy tiles, in order, from the decoder the
+ * kernel uses; *count = their number, at most cap triples written. Host only. */
+int nsm_set_h2d_bnb_persist(int form, int grid, int* prev);
+int nsm_conv1x1_dgrad_bnbwd_h2_plan(int M, int cip, int cop, int* plan);
+int nsm_h2d_tile_walk(int gx, int gy, int grid, int block, int* out, int cap, int* count);
 size_t nsm_conv1x1_wgrad_h2_ws(int M, int cin_p, int cout_p);
 /* (amax_k1dz, modes 0 / 1, may be NULL: the slot receiving max|scale * dz|,
  * nsm_bn_bwd_finalize's bound term for an h2 dY1 from nsm_bn_bwd_apply_h2) */

@@ -169,6 +169,379 @@ static WgradPlan plan_wgrad_h2(long long px, int cin_p, int cout_p) {
   return pl;
 }
 
+// ---- persistent form of the BN-backward input-gradient GEMM ---------------------
+// gemm_h2_kernel runs one output tile per block. With the short K of most 1x1
+// input gradients (2-4 K-tiles) every block pays descriptor setup, the Y1
+// prefetch, two K-tiles of DMA latency and a barrier before a handful of
+// MFMAs, then stages its whole wave tile through the LDS the stages used.
+// gemm_h2bp_kernel is gemm_h2p_kernel's scheme for this GEMM: a fixed grid
+// walks the tiles L = blockIdx.x, + gridDim.x, ... in the order of
+// h2d_tile_decode, the K-tile stream runs on ACROSS tiles (the last two
+// K-tiles of a tile refill their stages with the next tile's first two, the
+// loaders re-aimed), the next tile's first fragments load under the last
+// MFMAs, and the epilogue works from a staging region of its own, one 16-row
+// slab of the 64 x 64 wave tile at a time, so the next tile's DMA lands while
+// it runs. The Y1 rows of the NEXT tile are fetched slab by slab into the
+// registers the current slab has just consumed. MFMA shape, product order,
+// K order, epilogue arithmetic, per-lane row order, merge order and the
+// partial-row format are gemm_h2_kernel<..., EpiBnBwd>'s: the results are
+// bitwise those of the one-tile-per-block kernel at the same tile.
+//
+// The tile walk: logical index lg -> M block lg / gy, N block lg % gy (the N
+// tiles of one M block share its dY2 rows and its partial row, so they are
+// consecutive); with several N tiles and total % 8 == 0 the dispatch slot L
+// maps to lg XCD-contiguously (xcd_block_order mode 2, what launch_h2d uses).
+__host__ __device__ inline int h2d_tile_decode(int L, int gx, int gy, int& m, int& n) {
+  const int total = gx * gy;
+  const int lg = (gy > 1 && (total & 7) == 0) ? (L & 7) * (total >> 3) + (L >> 3) : L;
+  m = lg / gy;
+  n = lg - m * gy;
+  return lg;
+}
+
+// two waves per SIMD (two 4-wave blocks or one 8-wave block per CU): 256 registers
+template <int BM, int BN, int WM, int WN>
+__global__ void __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
+    gemm_h2bp_kernel(H2RowsP ap, H2RowsP bp, BnBwdEpiP ep, int M, int N, int K, int gx, int gy,
+                     H2Scale sca, H2Scale scb) {
+  constexpr int NW = WM * WN, TM = BM / (WM * 32), TN = BN / (WN * 32);
+  static_assert(TM == 2 && TN == 2, "64 x 64 wave tiles");
+  using AL = H2RowsDma<BM, NW>;
+  using BL = H2RowsDma<BN, NW>;
+  constexpr int KT = 64;
+  constexpr int A_EL = BM * KT, STAGE = (BM + BN) * KT;
+  constexpr int LPT = AL::NI + BL::NI;
+  constexpr int CPR = 16, NIT = 16;  // EpiBnBwd's lane layout of a 64 x 64 wave tile
+  constexpr int SLAB = 16 * 64;      // fp32 staging per wave: 16 rows of the wave tile
+  static_assert(LPT <= 63 && 2 * NIT <= 63, "vmcnt range");
+  __shared__ __attribute__((aligned(1024))) bf16_t lds[2 * STAGE + 2 * NW * SLAB];
+
+  const int total = gx * gy;
+  int L = blockIdx.x;
+  if (L >= total) return;  // no tile: out before the first barrier
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wid / WN, wn = wid % WN;
+  const int nk = K / KT;  // >= 2 (h2d_bnb_covered)
+  const float ia = exp2i(-h2_exp(sca)), ib = exp2i(-h2_exp(scb));
+  int bm, bn;
+  h2d_tile_decode(L, gx, gy, bm, bn);
+
+  const int arb = wm * TM * 32, brb = wn * TN * 32;
+  const int cc = lane % CPR, rq = lane / CPR;
+  const float* __restrict__ Y = (const float*)ep.y;
+  // Y1 rows of the first tile (EpiBnBwd::prefetch's layout), older than every DMA
+  f32x4 yv[NIT];
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int m = min(bm * BM + arb + it * 4 + rq, M - 1);
+    yv[it] = *(const f32x4*)(Y + (size_t)m * ep.ldy + bn * BN + brb + cc * 4);
+  }
+
+  AL a;
+  BL b;
+  a.rows(ap, wid, lane);
+  b.rows(bp, wid, lane);
+  a.aim(ap, bm * BM, 0);
+  b.aim(bp, bn * BN, 0);
+  a.prep(ap, 0);
+  b.prep(bp, 0);
+#pragma unroll
+  for (int j = 0; j < LPT; ++j) dma_one(a, b, ap, bp, lds, A_EL, wid, j);
+  a.prep(ap, KT);
+  b.prep(bp, KT);
+#pragma unroll
+  for (int j = 0; j < LPT; ++j) dma_one(a, b, ap, bp, lds + STAGE, A_EL, wid, j);
+  vm_wait<0>();  // both K-tiles (and Y1): the first tile's K-tile-1 wait then counts like every tile's
+  dma_barrier();
+
+  using FR = FragH2<false, KT>;
+  FR fa[2][2][TM];  // [k-step][plane][tm]
+  FR fb[2][2][TN];
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm) fa[0][p][tm].issue(lds, arb + tm * 32, lane, 0, p);
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn) fb[0][p][tn].issue(lds + A_EL, brb + tn * 32, lane, 0, p);
+  }
+  const __amdgpu_buffer_rsrc_t orsrc =
+      __builtin_amdgcn_make_buffer_rsrc(ep.out, (short)0, ep.out ? M * ep.ldo * 4 : 0, 0x00020000);
+  float* const stg = (float*)(lds + 2 * STAGE) + wid * SLAB;
+  const float* const stg0 = (const float*)(lds + 2 * STAGE);
+  const bool red = ep.mode != 2;
+  int st = 0;  // the stage of the K-tile at hand (an odd K-tile count flips it per tile)
+  for (; L < total; L += (int)gridDim.x) {
+    const bool has_next = L + (int)gridDim.x < total;
+    int bmn = 0, bnn = 0;
+    if (has_next) h2d_tile_decode(L + (int)gridDim.x, gx, gy, bmn, bnn);
+    f32x16 acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    for (int t = 0; t < nk; ++t) {
+      const bf16_t* As = lds + st * STAGE;
+      const bf16_t* Bs = As + A_EL;
+      // k-step 0: k-step 1's fragments go out, then k-step 0's MFMAs
+#pragma unroll
+      for (int p = 0; p < 2; ++p) {
+#pragma unroll
+        for (int tm = 0; tm < TM; ++tm) fa[1][p][tm].issue(As, arb + tm * 32, lane, 1, p);
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) fb[1][p][tn].issue(Bs, brb + tn * 32, lane, 1, p);
+      }
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) mfma_h2<TM, TN>(acc, fa[0], fb[0], tm, tn);
+      __builtin_amdgcn_s_setprio(0);
+      const int tgt = t + 2;  // the K-tile refilled into this stage (>= nk: the next tile's)
+      const bool more = t + 1 < nk || has_next, refill = tgt < nk || has_next;
+      if (refill) {
+        if (tgt < nk) {
+          a.prep(ap, tgt * KT);
+          b.prep(bp, tgt * KT);
+        } else {
+          if (tgt == nk) {
+            a.aim(ap, bmn * BM, 0);
+            b.aim(bp, bnn * BN, 0);
+          }
+          a.prep(ap, (tgt - nk) * KT);
+          b.prep(bp, (tgt - nk) * KT);
+        }
+      }
+      __builtin_amdgcn_s_waitcnt(0xC07F);  // this wave's reads of the stage retired
+      if (more) {
+        // this wave's pieces of the next K-tile. In a tile's first K-tile the
+        // previous tile's epilogue is younger than them: NIT Y1 loads, and NIT
+        // stores unless mode 0 (anything else it issued only makes the wait
+        // stricter). The first tile's K-tile 1 was waited for in the prologue.
+        // (t made opaque: a visible t == 0 test makes hipcc peel the first K-trip)
+        int tq = t;
+        asm volatile("" : "+s"(tq));
+        if (tq == 0) {
+          if (ep.mode == 0) vm_wait<NIT>();
+          else vm_wait<2 * NIT>();
+        } else {
+          vm_wait<0>();
+        }
+        __builtin_amdgcn_s_barrier();  // everyone's reads retired, pieces landed
+        const bf16_t* Ns = lds + (st ^ 1) * STAGE;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+#pragma unroll
+          for (int tm = 0; tm < TM; ++tm) fa[0][p][tm].issue(Ns, arb + tm * 32, lane, 0, p);
+#pragma unroll
+          for (int tn = 0; tn < TN; ++tn) fb[0][p][tn].issue(Ns + A_EL, brb + tn * 32, lane, 0, p);
+        }
+      }
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) {
+          mfma_h2<TM, TN>(acc, fa[1], fb[1], tm, tn);
+          if (refill) {
+            const int q = tm * TN + tn;
+#pragma unroll
+            for (int i = 0; i < LPT; ++i)
+              if (i * (TM * TN) / LPT == q) dma_one(a, b, ap, bp, As, A_EL, wid, i);
+          }
+        }
+      __builtin_amdgcn_s_setprio(0);
+      st ^= 1;
+    }
+
+    // ---- EpiBnBwd::apply_impl on 16-row slabs (same arithmetic, same order) ----
+    // lane offsets from an opaque copy of the lane index: formed here, not
+    // hoisted into registers that stay live across the K loop
+    int el = lane;
+    asm volatile("" : "+v"(el));
+    const int col = el & 31, h = el >> 5;
+    const int ec = el % CPR, er = el / CPR;
+    const int mb = bm * BM + arb, n = bn * BN + brb + ec * 4;
+    const int mbn = bmn * BM + arb, nn = bnn * BN + brb + ec * 4;
+    const float* __restrict__ mk = ep.mask;
+    const f32x4 sc = *(const f32x4*)(ep.scale + n), sh = *(const f32x4*)(ep.shift + n),
+                mu = *(const f32x4*)(ep.mean + n);
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 is = red ? *(const f32x4*)(ep.invstd + n) : zero;
+    const f32x4 k1 = red ? zero : *(const f32x4*)(ep.coef + n),
+                k2 = red ? zero : *(const f32x4*)(ep.coef + N + n),
+                k3 = red ? zero : *(const f32x4*)(ep.coef + 2 * N + n);
+    // the Dropout2d mask rows of the wave tile's 64 pixels: with HW >= 64 they
+    // lie in at most two images, whose rows are fetched here with the column
+    // vectors (a load per pixel row would drain the whole memory stream, the
+    // next tile's DMA and Y1 included, 16 times per tile); shorter images
+    // keep the load per row
+    const bool mrow = mk && ep.fdHW.d < 64u;
+    f32x4 mk0 = zero, mk1 = zero;
+    int mth = 0;
+    if (mk && !mrow) {
+      const uint32_t b0 = fdiv((uint32_t)min(mb, M - 1), ep.fdHW),
+                     b1 = fdiv((uint32_t)min(mb + 63, M - 1), ep.fdHW);
+      mk0 = *(const f32x4*)(mk + (size_t)b0 * N + n);
+      mk1 = *(const f32x4*)(mk + (size_t)b1 * N + n);
+      mth = (int)((b0 + 1u) * ep.fdHW.d);
+    }
+    // Every load of the epilogue but the next tile's Y1 is complete before the
+    // first slab: a register the compiler believes a load may still be writing
+    // on some path would cost a vmcnt(0) wherever the K loop reuses it, once
+    // per K-tile, and that wait would drain the DMA stream.
+    asm volatile("" ::"v"(sc), "v"(sh), "v"(mu), "v"(is), "v"(k1), "v"(k2), "v"(k3), "v"(mk0), "v"(mk1));
+    f32x4 s1 = zero, s2 = zero;
+    uint32_t am = 0;
+#pragma unroll
+    for (int sl = 0; sl < 4; ++sl) {
+      const int tm = sl >> 1, hf = sl & 1;
+#pragma unroll
+      for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          stg[((j & 3) + 8 * (j >> 2) + 4 * h) * 64 + tn * 32 + col] = (acc[tm][tn][8 * hf + j] * ia) * ib;
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int it = sl * 4 + q;
+        const int m = mb + it * 4 + er;
+        const bool ok = m < M;
+        const uint32_t ooff = ok ? (uint32_t)(m * ep.ldo + n) * 4u : OOB;
+        const f32x4 g = *(const f32x4*)&stg[(q * 4 + er) * 64 + ec * 4], v = yv[it];
+        f32x4 dz = g * lrelu_grad_v4(v * sc + sh, ep.slope);
+        if (mrow) dz = dz * *(const f32x4*)(mk + (size_t)fdiv((uint32_t)min(m, M - 1), ep.fdHW) * N + n);
+        else if (mk) dz = dz * (m < mth ? mk0 : mk1);
+        // rows past M by select, not by branch: every loaded register is
+        // consumed on every path (see the note at the column vectors)
+        if (!red) {
+          const f32x4 d = k1 * dz + k2 * (v - mu) + k3;
+          uint32_t a2 = am;
+          amax_fold(a2, d);
+          am = ok ? a2 : am;
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, d), orsrc, ooff, 0, 0);
+        } else {
+          const f32x4 t1 = s1 + dz, t2 = s2 + dz * ((v - mu) * is);
+          s1 = ok ? t1 : s1;
+          s2 = ok ? t2 : s2;
+          if (ep.k1dz) {
+            uint32_t a2 = am;
+            amax_fold(a2, sc * dz);
+            am = ok ? a2 : am;
+          }
+          if (ep.mode == 1)
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, g), orsrc, ooff, 0, 0);
+        }
+      }
+      // the next tile's Y1 rows into the registers this slab has consumed
+      if (has_next) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int it = sl * 4 + q;
+          const int m = min(mbn + it * 4 + er, M - 1);
+          yv[it] = *(const f32x4*)(Y + (size_t)m * ep.ldy + nn);
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    // the maxima go to a line chosen by the tile, not by the block that ran it
+    uint32_t* const aslot = red ? ep.k1dz : ep.amax;
+    if (aslot) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) am = max(am, (uint32_t)__shfl_xor((int)am, o));
+      const uint32_t line = ((uint32_t)bm + 7u * (uint32_t)bn) & (AMAX_LINES - 1);
+      if (el == 0 && am) atomicMax(aslot + line * AMAX_STRIDE, am);
+    }
+    if (red) {
+#pragma unroll
+      for (int o = CPR; o < 64; o <<= 1) {
+        s1 += shfl_xor_v4(s1, o);
+        s2 += shfl_xor_v4(s2, o);
+      }
+      // one partial row per BM rows: every wave leaves its sums in its own
+      // staging rows, the waves of one column range meet after a barrier,
+      // fixed order. The rows are next written in the next tile's epilogue,
+      // past a K-tile barrier that the reading waves reach after reading.
+      if (el < CPR) {
+        *(f32x4*)(stg + ec * 4) = s1;
+        *(f32x4*)(stg + 64 + ec * 4) = s2;
+      }
+      dma_barrier();
+      if (wm == 0) {
+        float* pr = ep.partial + (size_t)bm * 2 * N;
+        for (int j = el; j < 2 * 64; j += 64) {
+          const int k = j / 64, c = j - k * 64;
+          float t = 0.f;
+#pragma unroll
+          for (int w = 0; w < WM; ++w) t += stg0[(w * WN + wn) * SLAB + k * 64 + c];
+          pr[k * N + bn * BN + brb + c] = t;
+        }
+      }
+    }
+    bm = bmn;
+    bn = bnn;
+  }
+}
+
+// NSM_H2D_BNB_PERSIST: 0 = the one-tile-per-block kernel everywhere, 1 (default)
+// = the policy below, 2 = the persistent form wherever it covers the shape.
+// nsm_set_h2d_bnb_persist overrides (form 0 = policy, 1 = old, 2 = persistent;
+// grid = blocks of the persistent form, 0 = as many as are resident at once).
+static int g_h2d_bnb_form = [] {
+  const long long v = env_int("NSM_H2D_BNB_PERSIST", 1);
+  return v == 0 ? 1 : v == 2 ? 2 : 0;
+}();
+static int g_h2d_bnb_grid = 0;
+
+// shapes the persistent form takes: the 128-column tiles of 64 x 64 wave tiles,
+// whole N tiles, at least two K-tiles (a single K-tile, conv9's K = 64, would
+// need the DMA stream to run two TILES ahead: it stays on the old kernel),
+// 32-bit byte offsets into the output
+static bool h2d_bnb_covered(int tile, long long M, int N, int K, int ldo) {
+  return (tile == 2 || tile == 3) && N % 128 == 0 && K % 64 == 0 && K >= 128 &&
+         M * (long long)std::max(ldo, N) * 4 < (1ll << 31) &&
+         ceil_div(M, h2d_tile_bm(tile)) * (N / 128) < (1ll << 30);
+}
+// policy: more tiles than one round of resident blocks (two per CU of the
+// 128-row tile, one of the 256-row tile); otherwise every block has one tile
+// and the walk buys nothing
+static bool h2d_bnb_persistent(int tile, long long M, int N, int K, int ldo) {
+  if (g_h2d_bnb_form == 1 || !h2d_bnb_covered(tile, M, N, K, ldo)) return false;
+  if (g_h2d_bnb_form == 2) return true;
+  const long long tiles = ceil_div(M, h2d_tile_bm(tile)) * (N / 128);
+  return tiles > (long long)cu_count() * (tile == 3 ? 2 : 1);
+}
+
+template <int BM, int BN, int WM, int WN>
+static int h2bp_grid(long long total) {
+  static const int resident = [] {
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, gemm_h2bp_kernel<BM, BN, WM, WN>,
+                                                     WM * WN * 64, 0) != hipSuccess || occ < 1)
+      occ = 1;
+    return std::min(occ, 2) * cu_count();
+  }();
+  const long long g = g_h2d_bnb_grid > 0 ? g_h2d_bnb_grid : resident;
+  return (int)std::min<long long>(g, total);
+}
+
+template <int BM, int BN, int WM, int WN>
+static int launch_h2bp(const H2RowsP& ap, const H2RowsP& bp, const BnBwdEpiP& ep, int M, int N, int K,
+                       H2Scale sa, H2Scale sb, hipStream_t s) {
+  const int gx = ceil_div(M, BM), gy = N / BN;
+  const int grid = h2bp_grid<BM, BN, WM, WN>((long long)gx * gy);
+  hipLaunchKernelGGL((gemm_h2bp_kernel<BM, BN, WM, WN>), dim3(grid), dim3(WM * WN * 64), 0, s, ap, bp,
+                     ep, M, N, K, gx, gy, sa, sb);
+  NSM_LAUNCH_CHECK("conv1x1_h2 (persistent)");
+  return 0;
+}
+
 extern "C" int nsm_conv1x1_h2_rows(int M, int N, int K, int bnbwd) {
   return h2d_tile_bm(h2d_tile(M, N, K, bnbwd != 0));
 }
@@ -221,8 +594,69 @@ extern "C" int nsm_conv1x1_dgrad_bnbwd_h2(const void* dy2h, int M, int cop, cons
   const int K = 2 * cop;
   H2RowsP ap{(const bf16_t*)dy2h, K, M, 0};
   H2RowsP bp{(const bf16_t*)w2dh, K, cip, 0};
-  return gemm_h2d<EpiBnBwd>(h2d_tile(M, cip, K, true), ap, bp, ep, M, cip, K, H2Scale{amax_dy2, 1.f},
+  const int tile = h2d_tile(M, cip, K, true);
+  if (h2d_bnb_persistent(tile, M, cip, K, mode == 0 ? cip : ldo)) {
+    if (tile == 2)
+      return launch_h2bp<256, 128, 4, 2>(ap, bp, ep, M, cip, K, H2Scale{amax_dy2, 1.f},
+                                         H2Scale{amax_w, 1.f}, as_stream(stream));
+    return launch_h2bp<128, 128, 2, 2>(ap, bp, ep, M, cip, K, H2Scale{amax_dy2, 1.f},
+                                       H2Scale{amax_w, 1.f}, as_stream(stream));
+  }
+  return gemm_h2d<EpiBnBwd>(tile, ap, bp, ep, M, cip, K, H2Scale{amax_dy2, 1.f},
                             H2Scale{amax_w, 1.f}, as_stream(stream));
+}
+
+// the kernel form of nsm_conv1x1_dgrad_bnbwd_h2: form 0 = policy, 1 = one tile
+// per block, 2 = persistent wherever covered, < 0 = unchanged; grid = blocks
+// of the persistent form (0 = default, < 0 = unchanged). prev (optional)
+// receives the previous {form, grid}.
+extern "C" int nsm_set_h2d_bnb_persist(int form, int grid, int* prev) {
+  NSM_CHECK_ARG(form <= 2, "set_h2d_bnb_persist: form %d", form);
+  if (prev) {
+    prev[0] = g_h2d_bnb_form;
+    prev[1] = g_h2d_bnb_grid;
+  }
+  if (form >= 0) g_h2d_bnb_form = form;
+  if (grid >= 0) g_h2d_bnb_grid = grid;
+  return 0;
+}
+
+// what nsm_conv1x1_dgrad_bnbwd_h2 launches for (M, cip, cop) with a contiguous
+// output: plan[0] = tile (h2d_tile's numbering), plan[1] = form (0 = one tile
+// per block, 1 = persistent), plan[2] = blocks of the persistent form (0 for
+// form 0), plan[3] = rows per partial row
+extern "C" int nsm_conv1x1_dgrad_bnbwd_h2_plan(int M, int cip, int cop, int* plan) {
+  NSM_CHECK_ARG(plan && M > 0 && cip > 0 && cop > 0 && cip % 32 == 0 && cop % 32 == 0,
+                "conv1x1_dgrad_bnbwd_h2_plan: bad args");
+  const int K = 2 * cop, tile = h2d_tile(M, cip, K, true), bm = h2d_tile_bm(tile);
+  const bool p = h2d_bnb_persistent(tile, M, cip, K, cip);
+  const long long total = (long long)ceil_div(M, bm) * ceil_div(cip, 128);
+  plan[0] = tile;
+  plan[1] = p ? 1 : 0;
+  plan[2] = !p ? 0 : tile == 2 ? h2bp_grid<256, 128, 4, 2>(total) : h2bp_grid<128, 128, 2, 2>(total);
+  plan[3] = bm;
+  return 0;
+}
+
+// the tiles block `block` of a persistent grid of `grid` blocks walks over a
+// gx x gy tile space, in order: out[3 i] = M block, [3 i + 1] = N block,
+// [3 i + 2] = logical index (h2d_tile_decode). *count = their number (at most
+// cap are written). Host only: no device is touched.
+extern "C" int nsm_h2d_tile_walk(int gx, int gy, int grid, int block, int* out, int cap,
+                                 int* count) {
+  NSM_CHECK_ARG(out && count && gx > 0 && gy > 0 && grid > 0 && block >= 0 && block < grid &&
+                    cap >= 0 && (long long)gx * gy < (1ll << 30),
+                "h2d_tile_walk: bad args");
+  int cnt = 0;
+  for (int L = block; L < gx * gy; L += grid, ++cnt) {
+    if (cnt >= cap) continue;
+    int m, n;
+    out[3 * cnt + 2] = h2d_tile_decode(L, gx, gy, m, n);
+    out[3 * cnt] = m;
+    out[3 * cnt + 1] = n;
+  }
+  *count = cnt;
+  return 0;
 }
 
 extern "C" size_t nsm_conv1x1_wgrad_h2_ws(int M, int cin_p, int cout_p) {

@@ -76,6 +76,9 @@ _SIGS = {
     "nsm_conv1x1_h2": (I, [P, I, I, P, P, I, P, I, P, P, P, P]),
     "nsm_conv1x1_dgrad_bnbwd_h2": (I, [P, I, I, P, I, P, I, P, P, P, P, P, I, F, I, P, P, P, I, P,
                                        P, P, P, P]),
+    "nsm_set_h2d_bnb_persist": (I, [I, I, P]),
+    "nsm_conv1x1_dgrad_bnbwd_h2_plan": (I, [I, I, I, P]),
+    "nsm_h2d_tile_walk": (I, [I, I, I, I, P, I, P]),
     "nsm_conv3x3_h2_rows": (I, [I, I]),
     "nsm_conv3x3_h2": (I, [P, I, I, I, I, P, P, I, P, I, P, P, P, P]),
     "nsm_conv3x3_wgrad_h2_ws": (Z, [I, I, I, I, I]),

@@ -481,6 +481,45 @@ def wino_gemm_h2_plan(B, H, W, cin_p, cout_p, tile):
     return plan[0], H2_GEMM_FORMS[plan[1]]
 
 
+H2D_BNB_FORMS = ("policy", "old", "persistent")
+
+
+def set_h2d_bnb_persist(form=-1, grid=-1):
+    """Kernel form of conv1x1_dgrad_bn_bwd_h2 (nsm_set_h2d_bnb_persist): form
+    0 / "policy", 1 / "old" (one tile per block), 2 / "persistent" (wherever the
+    form covers the shape), -1 = unchanged; grid = blocks of the persistent
+    form, 0 = default, -1 = unchanged. Returns the previous (form, grid)."""
+    import ctypes
+    if isinstance(form, str):
+        form = H2D_BNB_FORMS.index(form)
+    prev = (ctypes.c_int * 2)()
+    call("nsm_set_h2d_bnb_persist", int(form), int(grid), prev)
+    return prev[0], prev[1]
+
+
+def conv1x1_dgrad_bnbwd_h2_plan(M, cip, cop):
+    """(tile, form "old" / "persistent", persistent grid, rows per partial row)
+    conv1x1_dgrad_bn_bwd_h2 runs for this shape on this device
+    (nsm_conv1x1_dgrad_bnbwd_h2_plan)."""
+    import ctypes
+    plan = (ctypes.c_int * 4)()
+    call("nsm_conv1x1_dgrad_bnbwd_h2_plan", M, cip, cop, plan)
+    return plan[0], ("old", "persistent")[plan[1]], plan[2], plan[3]
+
+
+def h2d_tile_walk(gx, gy, grid, block):
+    """[(M block, N block, logical index)] that block `block` of a persistent
+    grid of `grid` blocks visits over gx x gy tiles (nsm_h2d_tile_walk, host
+    only: the decoder the kernel uses)."""
+    import ctypes
+    cap = -(-gx * gy // grid)
+    out = (ctypes.c_int * (3 * max(cap, 1)))()
+    cnt = ctypes.c_int(0)
+    call("nsm_h2d_tile_walk", gx, gy, grid, block, out, cap, ctypes.byref(cnt))
+    assert cnt.value <= cap
+    return [(out[3 * i], out[3 * i + 1], out[3 * i + 2]) for i in range(cnt.value)]
+
+
 def wino_wgrad_h2_plan(B, H, W, cin_p, cout_p, tile):
     """(BM, BN, splits, kchunk) of nsm_conv3x3_wgrad_wino_h2 for this shape
     (nsm_wino_wgrad_h2_plan)."""
