@@ -313,6 +313,13 @@ int nsm_wino_gemm_h2(const void* V, const void* U, int B, int H, int W, int cin_
  * splits K slabs of kchunk Winograd tiles each, the last one shorter). */
 int nsm_wino_gemm_h2_plan(int B, int H, int W, int cin_p, int cout_p, int tile, int* plan);
 int nsm_wino_wgrad_h2_plan(int B, int H, int W, int cin_p, int cout_p, int tile, int* plan);
+/* The same for the bf16 path's single-plane GEMMs: nsm_wino_gemm_f16_plan ->
+ * plan[0] = the tile nsm_wino_gemm_f16 (o16 0) / nsm_wino_gemm_f16m (o16 1)
+ * runs (1: 256x256, 2: 256x128), plan[1] = the kernel form (1: gemm_h2q, 2:
+ * the persistent gemm_h2p); nsm_wino_wgrad_f16_plan -> {BM, BN, splits,
+ * kchunk} of nsm_conv3x3_wgrad_wino_f16. cin_p, cout_p multiples of 128. */
+int nsm_wino_gemm_f16_plan(int B, int H, int W, int cin_p, int cout_p, int tile, int o16, int* plan);
+int nsm_wino_wgrad_f16_plan(int B, int H, int W, int cin_p, int cout_p, int tile, int* plan);
 /* ---- the DoubleConv's 1x1 convolution on h2 operands (csrc/nsm_conv_h2d.inc)
  * Replaces nn.Conv2d(in, out, 1) (Unetmodel.py:26), its input gradient with
  * the first BN's backward fused (as nsm_conv1x1_dgrad_bnbwd) and its weight

@@ -3298,8 +3298,12 @@ extern "C" int nsm_wino_gemm_f16(const void* V, const void* U, int B, int H, int
                        H2Scale{amax_v, beta_v}, H2Scale{amax_u, beta_u}, as_stream(stream));
 }
 
-// the same GEMM writing M as f16 (O16: scale 2^-(15 + ceil log2 cin_p) in the
-// operands' scaled units; M16 [alpha^2][T][cout_p] f16, half of Mb's bytes)
+// the same GEMM writing M as f16 (O16): M16 [alpha^2][T][cout_p] f16 =
+// rn(acc 2^e_t) in the operands' scaled units, half of Mb's bytes, with one
+// exponent e_t = 15 - ceil log2(max|acc|) per 64 x 64 tile of each component
+// taken from that tile's own accumulators (0 for an all-zero tile) and written
+// to m16e [alpha^2][ceil(T/64)][cout_p/64]; the output transform multiplies by
+// 2^clamp(-e_t - e_v, -126, 126) 2^-e_u
 extern "C" int nsm_wino_gemm_f16m(const void* V, const void* U, int B, int H, int W, int cin_p,
                                   int cout_p, int tile, void* M16, int* m16e, const uint32_t* amax_v,
                                   float beta_v, const uint32_t* amax_u, float beta_u, void* stream) {

@@ -160,6 +160,18 @@ extern "C" int nsm_wino_gemm_h2_plan(int B, int H, int W, int cin_p, int cout_p,
   return 0;
 }
 
+extern "C" int nsm_wino_gemm_f16_plan(int B, int H, int W, int cin_p, int cout_p, int tile, int o16,
+                                      int* plan) {
+  WinoGeom g;
+  NSM_CHECK_ARG(plan && wino_geom(tile, B, H, W, g) && cin_p > 0 && cout_p > 0 && cin_p % 128 == 0 &&
+                    cout_p % 128 == 0 && (o16 == 0 || o16 == 1),
+                "wino_gemm_f16_plan: bad args");
+  const WinoGemmF16Plan p = plan_wino_gemm_f16(g.T, cin_p, cout_p, g.alpha2);
+  plan[0] = p.tile;
+  plan[1] = p.form;
+  return 0;
+}
+
 // the weight-gradient plan of the f16 path: the h2 plan's, on its 256 / 128 tiles
 // (the bf16 path's Winograd weight gradient, nsm_conv.hip; declared in nsm_conv.h)
 WinoWgradPlan nsm::plan_wino_wgrad_f16(long long T, int cin_p, int cout_p, int nb) {
@@ -224,4 +236,18 @@ WinoWgradPlan nsm::plan_wino_wgrad_f16(long long T, int cin_p, int cout_p, int n
   p.slab_floats = (size_t)nb * sp * cout_p * cin_p;
   if (sp > 1) p.slab_floats += (size_t)nb * cout_p * cin_p;
   return p;
+}
+
+extern "C" int nsm_wino_wgrad_f16_plan(int B, int H, int W, int cin_p, int cout_p, int tile,
+                                       int* plan) {
+  WinoGeom g;
+  NSM_CHECK_ARG(plan && wino_geom(tile, B, H, W, g) && cin_p > 0 && cout_p > 0 && cin_p % 128 == 0 &&
+                    cout_p % 128 == 0,
+                "wino_wgrad_f16_plan: bad args");
+  const WinoWgradPlan p = plan_wino_wgrad_f16(g.T, cin_p, cout_p, g.alpha2);
+  plan[0] = p.BM;
+  plan[1] = p.BN;
+  plan[2] = p.splits;
+  plan[3] = p.kchunk;
+  return 0;
 }

@@ -1088,11 +1088,13 @@ static int launch_h2p(dim3 grid, hipStream_t s, const typename AL::P& ap, const 
   return 0;
 }
 
+// gemm_h2p_kernel (persistent) or gemm_h2q_kernel (one tile per block), as the
+// caller's plan decided
 template <int BM, int BN, int WM, int WN, class AL, class BL, bool SP = false, bool O16 = false>
-static int launch_h2q_or_p(dim3 grid, hipStream_t s, const typename AL::P& ap,
+static int launch_h2q_or_p(bool persistent, dim3 grid, hipStream_t s, const typename AL::P& ap,
                            const typename BL::P& bp, const EpiH2P& ep, int M, int N, int K,
                            H2Scale sa, H2Scale sb) {
-  if (h2_persistent((long long)grid.x * grid.y * grid.z, K))
+  if (persistent)
     return launch_h2p<BM, BN, WM, WN, AL, BL, SP, O16>(grid, s, ap, bp, ep, M, N, K, sa, sb);
   return launch_h2q<BM, BN, WM, WN, AL, BL, SP, O16>(grid, s, ap, bp, ep, M, N, K, sa, sb);
 }
@@ -1100,6 +1102,19 @@ static int launch_h2q_or_p(dim3 grid, hipStream_t s, const typename AL::P& ap,
 // NSM_H2_TILE: force the forward / dgrad tile (0 = policy, 1 = 256x256,
 // 2 = 256x128, 3 = 128x128)
 static int h2_tile_env() { static const int v = (int)env_int("NSM_H2_TILE", 0); return v; }
+
+// The single-plane GEMM's decision, shared by the launch below and the query
+// entry nsm_wino_gemm_f16_plan: tile 1 = 256x256 (cout_p % 256 == 0), 2 =
+// 256x128; form 1 = gemm_h2q_kernel, 2 = gemm_h2p_kernel. The same for fp32
+// and f16 M.
+struct WinoGemmF16Plan {
+  int tile, form;
+};
+static WinoGemmF16Plan plan_wino_gemm_f16(long long T, int cin_p, int cout_p, int nb) {
+  const int tile = cout_p % 256 == 0 ? 1 : 2;
+  const long long total = (long long)ceil_div((int)T, 256) * (cout_p / (tile == 1 ? 256 : 128)) * nb;
+  return WinoGemmF16Plan{tile, h2_persistent(total, cin_p) ? 2 : 1};
+}
 
 // batched M = T x N = cout GEMMs over K = cin channels of single-plane scaled
 // f16 operands (the bf16 path's Winograd forward: V [nb][T][cin_p], U
@@ -1116,13 +1131,15 @@ int nsm::wino_gemm_f16(const bf16_t* V, const bf16_t* U, long long T, int cin_p,
   const dim3 g256(ceil_div(M, 256), N / 256, nb), g128(ceil_div(M, 256), N / 128, nb);
   using R256 = H2RowsDma<256, 8>;
   using R128 = H2RowsDma<128, 8>;
+  const WinoGemmF16Plan pl = plan_wino_gemm_f16(T, cin_p, cout_p, nb);
+  const bool pers = pl.form == 2;
   if (o16)
-    return N % 256 == 0
-               ? launch_h2q_or_p<256, 256, 2, 4, R256, R256, true, true>(g256, s, ap, bp, ep, M, N, K, sv, su)
-               : launch_h2q_or_p<256, 128, 4, 2, R256, R128, true, true>(g128, s, ap, bp, ep, M, N, K, sv, su);
-  return N % 256 == 0
-             ? launch_h2q_or_p<256, 256, 2, 4, R256, R256, true>(g256, s, ap, bp, ep, M, N, K, sv, su)
-             : launch_h2q_or_p<256, 128, 4, 2, R256, R128, true>(g128, s, ap, bp, ep, M, N, K, sv, su);
+    return pl.tile == 1
+               ? launch_h2q_or_p<256, 256, 2, 4, R256, R256, true, true>(pers, g256, s, ap, bp, ep, M, N, K, sv, su)
+               : launch_h2q_or_p<256, 128, 4, 2, R256, R128, true, true>(pers, g128, s, ap, bp, ep, M, N, K, sv, su);
+  return pl.tile == 1
+             ? launch_h2q_or_p<256, 256, 2, 4, R256, R256, true>(pers, g256, s, ap, bp, ep, M, N, K, sv, su)
+             : launch_h2q_or_p<256, 128, 4, 2, R256, R128, true>(pers, g128, s, ap, bp, ep, M, N, K, sv, su);
 }
 
 // The forward / dgrad GEMM's decision, shared by the launch below and the

@@ -43,6 +43,8 @@ _SIGS = {
     "nsm_wino_gemm_h2": (I, [P, P, I, I, I, I, I, I, P, P, F, P, F, P]),
     "nsm_wino_gemm_h2_plan": (I, [I, I, I, I, I, I, P]),
     "nsm_wino_wgrad_h2_plan": (I, [I, I, I, I, I, I, P]),
+    "nsm_wino_gemm_f16_plan": (I, [I, I, I, I, I, I, I, P]),
+    "nsm_wino_wgrad_f16_plan": (I, [I, I, I, I, I, I, P]),
     "nsm_wino_beta": (F, [I, I]),
     "nsm_wino_input_h2": (I, [P, I, I, I, I, I, I, I, I, P, P, P]),
     "nsm_wino_dual_input_h2": (I, [P, I, I, I, I, I, I, P, P, P, P]),

@@ -529,6 +529,25 @@ def wino_wgrad_h2_plan(B, H, W, cin_p, cout_p, tile):
     return tuple(plan)
 
 
+def wino_gemm_f16_plan(B, H, W, cin_p, cout_p, m16=False):
+    """(tile 1: 256x256 / 2: 256x128, kernel form) nsm_wino_gemm_f16 (m16:
+    nsm_wino_gemm_f16m) runs for this shape on this device
+    (nsm_wino_gemm_f16_plan)."""
+    import ctypes
+    plan = (ctypes.c_int * 2)()
+    call("nsm_wino_gemm_f16_plan", B, H, W, cin_p, cout_p, 4, int(bool(m16)), plan)
+    return plan[0], H2_GEMM_FORMS[plan[1]]
+
+
+def wino_wgrad_f16_plan(B, H, W, cin_p, cout_p):
+    """(BM, BN, splits, kchunk) of nsm_conv3x3_wgrad_wino_f16 for this shape
+    (nsm_wino_wgrad_f16_plan)."""
+    import ctypes
+    plan = (ctypes.c_int * 4)()
+    call("nsm_wino_wgrad_f16_plan", B, H, W, cin_p, cout_p, 4, plan)
+    return tuple(plan)
+
+
 def wino_dual_input_h2(dy, B, H, W, tile, amax_dy):
     """wino_dual_input writing (Vd, dM) as h2 tensors; amax_dy: max|dy| slot
     (filled by dy's producer), their scale source."""

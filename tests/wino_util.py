@@ -315,11 +315,12 @@ def slot_value(slot):
     return float(np.array(v, dtype=np.uint32).view(np.float32))
 
 
-def tiny_share(ref, P):
-    """Share of ref's non-zero elements below 2^-17 of P."""
+def tiny_share(ref, P, rel=S.TINY_REL):
+    """Share of ref's non-zero elements below rel (2^-17: where l turns
+    subnormal) of P; P a number or a tensor broadcast against ref."""
     a = ref.abs()
     nz = a > 0
-    return ((a < S.TINY_REL * P) & nz).double().sum().item() / max(1, int(nz.sum()))
+    return ((a < rel * P) & nz).double().sum().item() / max(1, int(nz.sum()))
 
 
 # ---- GEMM stages ----------------------------------------------------------------------
