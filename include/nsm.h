@@ -1210,6 +1210,51 @@ int nsm_frame_prep(const float* x, int B, int C, int H, int W, int Hp, int Wp, c
 int nsm_frame_finish(const float* o, int B, int C, int Hp, int Wp, int H, int W, uint8_t* u8,
                      float* f32, uint32_t* partial, int32_t* report, void* stream);
 
+/* ---- training-patch sampler (csrc/nsm_patch.hip) -------------------
+ * nsm_patch_gather: one launch writes a batch of crops out of a device-resident
+ *   pool: inputs [N][C][H][W] f32 and labels [N][E][H][W] f32 (E >= 1 target
+ *   planes, one per emitter size) -> x_out [B][C][ph][pw] f32 normalised,
+ *   y_out [B][1][ph][pw] f32, and (draws_out != NULL) draws_out [B][8] int32 =
+ *   frame, oy, ox, hflip, vflip, emitter index, 0, 0 of each sample.
+ *   Draws: sample i of step t is n = t * B + i (uint64, wrapping); field f is
+ *     r_f = mix64((seed ^ mix64(rank)) ^ mix64(8 n + f)), mix64 the splitmix64
+ *     finaliser of csrc/nsm_common.h; draw(m) = the high 64 bits of r_f * m.
+ *     f = 0 the frame: order 0 (sequential) lo + n mod count, order 1 (random)
+ *     lo + draw(count); f = 1: oy = align * draw((H - ph) / align + 1); f = 2:
+ *     ox = align * draw((W - pw) / align + 1); f = 3: hflip = the top bit of r_3
+ *     (hflip != 0, else 0), vflip = the next bit (vflip != 0, else 0); f = 4:
+ *     e = draw(E). [lo, lo + count) is the caller's shard of the N frames.
+ *   The seed is `seed` or, with seed_dev, the device int64 word read by the
+ *     kernel; the step t is `step` or, with step_dev, the device int64 word.
+ *   Values: x = ((s * v + o) - mean[c]) / (stdv[c] + eps) in fp32, one rounding
+ *     per operation (no contraction): the expression and the bits of
+ *     nsm_normalize_frames behind s * v + o. v = inputs[frame][c][oy + r'][ox + q']
+ *     with r' = vflip ? ph - 1 - r : r and q' = hflip ? pw - 1 - q : q; s =
+ *     (hflip ? hsign[c] : 1) * (vflip ? vsign[c] : 1) (hsign / vsign [C], NULL:
+ *     all ones); o = emitter_values[e] is added where c == emitter_channel and
+ *     nowhere else (emitter_channel -1 and emitter_values NULL: no emitter; both
+ *     or neither). mean / stdv [C] are required (0, 1 and eps 0 give the raw
+ *     values bit for bit). y = labels[frame][e] cropped and mirrored the same
+ *     way, copied bit for bit.
+ *   Limits (NSM_E_ARG otherwise): ph <= H, pw <= W, align >= 1, count >= 1,
+ *     0 <= lo, lo + count <= N < 2^31, C <= 256, C*H*W < 2^31 and E*H*W < 2^31
+ *     (offsets inside a frame are 32 bits; the frame base is 64 bits, a pool
+ *     may hold any number of elements). Stores are 16 bytes wide when
+ *     pw % 4 == 0 and x_out / y_out are 16-byte aligned, 4 bytes otherwise
+ *     (4-byte alignment is required). No atomics, no host synchronisation, no
+ *     allocation; asynchronous on `stream` and capturable.
+ * nsm_patch_advance: step_dev[0] += 1, a one-thread launch: queued behind the
+ *   gather on the same stream, a captured graph holding both draws a new batch
+ *   at every replay. */
+int nsm_patch_gather(const float* inputs, const float* labels, int64_t N, int C, int E, int H,
+                     int W, int B, int ph, int pw, const float* mean, const float* stdv, float eps,
+                     const float* hsign, const float* vsign, int emitter_channel,
+                     const float* emitter_values, int order, int align, int hflip, int vflip,
+                     int64_t lo, int64_t count, int rank, uint64_t seed, const int64_t* seed_dev,
+                     int64_t step, const int64_t* step_dev, float* x_out, float* y_out,
+                     int32_t* draws_out, void* stream);
+int nsm_patch_advance(int64_t* step_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

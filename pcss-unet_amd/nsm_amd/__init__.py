@@ -17,6 +17,7 @@ from .optim import (FlatAdam, FlatAdamW, FlatSGD, allreduce_grads, flat_grad,  #
 from .grad_scaler import GradScaler  # noqa: F401
 from .infer import GraphedUnet  # noqa: F401
 from .frames import FramePipeline, finish_frames, prepare_frames  # noqa: F401
+from .patches import PatchSampler, patch_draws  # noqa: F401
 from .sensitivity import (FeatureSensitivity, SensitivityResult,  # noqa: F401
                           feature_sensitivity)
 from .stats import (ChannelStats, StatsResult, channel_stats, dataset_stats,  # noqa: F401

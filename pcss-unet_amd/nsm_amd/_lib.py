@@ -173,6 +173,9 @@ _SIGS = {
     "nsm_frame_blocks": (I, [I, I, I]),
     "nsm_frame_prep": (I, [P, I, I, I, I, I, I, P, P, F, I, P, P, P, P]),
     "nsm_frame_finish": (I, [P, I, I, I, I, I, I, P, P, P, P, P]),
+    "nsm_patch_gather": (I, [P, P, L, I, I, I, I, I, I, I, P, P, F, P, P, I, P, I, I, I, I, L, L, I,
+                             U64, P, L, P, P, P, P, P]),
+    "nsm_patch_advance": (I, [P, P]),
     "nsm_pack_conv_weight_bf16": (I, [P, I, I, I, I, I, I, P, P]),
     "nsm_conv_fwd_bf16": (I, [P, I, I, I, I, I, P, P, I, I, P, I, P, P, P, F, P, P]),
     "nsm_conv_wgrad_bf16_ws": (Z, [I, I, I, I, I, I]),
