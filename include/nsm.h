@@ -1255,6 +1255,44 @@ int nsm_patch_gather(const float* inputs, const float* labels, int64_t N, int C,
                      int32_t* draws_out, void* stream);
 int nsm_patch_advance(int64_t* step_dev, void* stream);
 
+/* ---- G-buffer feature recipes (csrc/nsm_features.hip) ---------------
+ * nsm_feature_compose: x [B][Cin][H][W] fp32 (the rasteriser's raw buffers) ->
+ *   out [B][Cout][Hp][Wp] fp32 (the network's input channels) in one streaming
+ *   pass. recipe is a HOST table [Cout][3] of (op, a, b); it is read during the
+ *   call and travels to the kernel by value, so a captured graph holds it and
+ *   nothing is uploaded. Output channel c at output pixel (y, x) is, over the raw
+ *   values at the source pixel (ry, rx), ry = y < H ? y : 2 * (H - 1) - y and rx
+ *   likewise (nsm_frame_prep's reflection, with its limits Hp - H < H, Wp - W < W):
+ *     op 0 RAW    x[a]                                  (bits unchanged; b ignored)
+ *     op 1 SUB    x[a] - x[b]
+ *     op 2 RATIO  |x[b]| <= ratio_floor ? +0.0 : x[a] / x[b]  (correctly rounded;
+ *                 a NaN x[b] is not below the floor: the division gives NaN)
+ *     op 3 DOT3   ((x[a] * x[b]) + (x[a+1] * x[b+1])) + (x[a+2] * x[b+2])
+ *   one IEEE fp32 operation per step, no contraction. Then, in this order:
+ *     census (partial and report both or neither): report[b][0..2] = the NaN,
+ *       +Inf and -Inf among the composed values of image b's own Cout*H*W pixels
+ *       (a reflected copy is not counted), the layout of nsm_frame_prep; partial
+ *       holds B * nsm_feature_blocks(Cout, Hp, Wp) * 3 words;
+ *     scrub != 0: NaN -> 0, +Inf -> 1, -Inf -> 0, finite bits kept;
+ *     c == emitter_channel: v + emitter[b], emitter a DEVICE vector [B] (a
+ *       captured graph follows new values); no other channel is touched.
+ *       emitter_channel -1 and emitter NULL: none (both or neither);
+ *     mean / stdv [Cout] (both or neither): (v - mean[c]) / (stdv[c] + eps), the
+ *       expression and the bits of nsm_normalize_frames.
+ *   Limits (NSM_E_ARG before any launch otherwise): 1 <= Cout <= 16, 1 <= Cin <= 64,
+ *     every channel a term reads inside [0, Cin) (DOT3: a + 2 and b + 2 too),
+ *     ratio_floor >= 0, Cin*H*W < 2^31 and Cout*Hp*Wp < 2^31. Pointers are 4-byte
+ *     aligned; 16-byte accesses are used wherever an address allows. No atomics,
+ *     no host synchronisation, no allocation; capturable.
+ * nsm_feature_blocks: blocks per image of that pass (0: a dimension < 1, Cout
+ *   above 16, or Cout*Hp*Wp >= 2^31). */
+int nsm_feature_blocks(int Cout, int Hp, int Wp);
+int nsm_feature_compose(const float* x, int B, int Cin, int H, int W, int Hp, int Wp,
+                        const int32_t* recipe, int Cout, float ratio_floor, const float* mean,
+                        const float* stdv, float eps, int scrub, int emitter_channel,
+                        const float* emitter, float* out, uint32_t* partial, int32_t* report,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,42 +35,13 @@
 //     t + 256, ..., and the threads by the same tree: whole numbers in a fixed
 //     order, no atomics, and no second pass over the frame.
 #include <math.h>
-#include "nsm_common.h"
+#include "nsm_frame.h"
 
 namespace nsm {
 
 // 2 units per thread: measured against 1 and 4 at 1080p ("Inference frame path")
-constexpr int FR_THREADS = 256, FR_PER_THREAD = 2;
+constexpr int FR_PER_THREAD = 2;
 constexpr int FR_UNITS = FR_THREADS * FR_PER_THREAD;  // units of one block: 2048 samples
-
-// torch.nan_to_num(nan=0.0, posinf=1.0, neginf=0.0): selects only, so every
-// finite value (-0.0, denormals, FLT_MAX) keeps its bits
-__device__ __forceinline__ float frame_scrub(float v) {
-  const uint32_t u = __float_as_uint(v);
-  if ((u & 0x7fffffffu) < 0x7f800000u) return v;
-  return u == 0x7f800000u ? 1.f : 0.f;
-}
-
-// the three counts of a block -> part[0..2]; every thread of the block calls
-__device__ __forceinline__ void frame_block_counts(uint32_t a, uint32_t b, uint32_t c,
-                                                   uint32_t* __restrict__ part) {
-  __shared__ uint32_t sh[FR_THREADS / 64][3];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    a += __shfl_down(a, off, 64);
-    b += __shfl_down(b, off, 64);
-    c += __shfl_down(c, off, 64);
-  }
-  const int t = threadIdx.x;
-  if ((t & 63) == 0) sh[t >> 6][0] = a, sh[t >> 6][1] = b, sh[t >> 6][2] = c;
-  __syncthreads();
-  if (t < 3) {
-    uint32_t s = 0;
-#pragma unroll
-    for (int w = 0; w < FR_THREADS / 64; ++w) s += sh[w][t];
-    part[t] = s;
-  }
-}
 
 struct PrepArgs {
   const float* x;
@@ -219,24 +190,6 @@ __global__ void __launch_bounds__(FR_THREADS) frame_finish_kernel(FinishArgs a) 
     }
   }
   if (a.part) frame_block_counts(n_bad, n_neg, n_big, a.part + (size_t)blockIdx.x * 3);
-}
-
-// grid: B blocks. report[b][off .. off + 2] = the sums of image b's `per` triples
-__global__ void __launch_bounds__(FR_THREADS)
-    frame_census_kernel(const uint32_t* __restrict__ part, int per, int off,
-                        int32_t* __restrict__ report) {
-  const uint32_t* p = part + (size_t)blockIdx.x * per * 3;
-  uint32_t s[3] = {0, 0, 0};
-  for (int i = threadIdx.x; i < per; i += FR_THREADS) {
-    s[0] += p[3 * i], s[1] += p[3 * i + 1], s[2] += p[3 * i + 2];
-  }
-  frame_block_counts(s[0], s[1], s[2], (uint32_t*)report + (size_t)blockIdx.x * 6 + off);
-}
-
-static void frame_census(const uint32_t* part, int B, int per, int off, int32_t* report,
-                         hipStream_t st) {
-  hipLaunchKernelGGL(frame_census_kernel, dim3((unsigned)B), dim3(FR_THREADS), 0, st, part, per,
-                     off, report);
 }
 
 }  // namespace nsm

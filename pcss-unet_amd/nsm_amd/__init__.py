@@ -16,7 +16,9 @@ from .optim import (FlatAdam, FlatAdamW, FlatSGD, allreduce_grads, flat_grad,  #
                     make_optimizer)
 from .grad_scaler import GradScaler  # noqa: F401
 from .infer import GraphedUnet  # noqa: F401
-from .frames import FramePipeline, finish_frames, prepare_frames  # noqa: F401
+from .features import FeatureRecipe  # noqa: F401
+from .frames import (FramePipeline, compose_features, finish_frames,  # noqa: F401
+                     prepare_frames)
 from .patches import PatchSampler, patch_draws  # noqa: F401
 from .sensitivity import (FeatureSensitivity, SensitivityResult,  # noqa: F401
                           feature_sensitivity)

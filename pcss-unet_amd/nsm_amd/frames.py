@@ -26,6 +26,14 @@ The census `report` is an int32 [B,6] device tensor (`new_report`):
 columns 0-2 the NaN, +Inf and -Inf among an image's raw samples (prepare_frames),
 columns 3-5 the non-finite, the < 0 and the > 1 samples of the (cropped) network
 output before the scrub and the clip (finish_frames); REPORT_KEYS names them.
+
+A renderer that has the rasteriser's raw buffers and a model trained on channels
+composed from them (features.FeatureRecipe) passes the recipe:
+`compose_features` (csrc/nsm_features.hip, nsm_feature_compose) is
+prepare_frames with the composition in front of the scrub and the emitter
+offset of the paper's §3.1.1 behind it, still one pass, and
+`FramePipeline(model, raw_example, recipe=..., emitter_channel=...)` captures it
+in place of prepare_frames; columns 0-2 then count the composed values.
 """
 import os
 
@@ -33,6 +41,7 @@ import torch
 
 from ._lib import call, lib, ptr, stream
 from .data import MmapLiverDataset, _given_stats, load_stats
+from .features import FeatureRecipe
 from .infer import GraphedUnet
 
 REPORT_KEYS = ("nan", "posinf", "neginf", "out_nonfinite", "out_below_zero", "out_above_one")
@@ -142,6 +151,79 @@ def prepare_frames(x, *, pad_multiple=16, stats=None, scrub=True, eps=MmapLiverD
     return out
 
 
+def _emitter_of(emitter, B, device):
+    """The emitter offsets as a device [B] fp32 tensor: a float (every image), a
+    sequence of B floats, or such a tensor itself."""
+    if torch.is_tensor(emitter) and emitter.is_cuda:
+        return _check_buffer(emitter, (B,), torch.float32, device, "compose_features: emitter")
+    try:
+        e = torch.as_tensor(emitter, dtype=torch.float32).reshape(-1)
+    except (TypeError, ValueError, RuntimeError):
+        e = None
+    if e is None or e.numel() not in (1, B):
+        raise ValueError(f"compose_features: emitter must be a number, {B} numbers (one per image) "
+                         f"or a [{B}] float32 tensor on {device}, got {emitter!r}")
+    return e.expand(B).contiguous().to(device)
+
+
+def compose_features(x, recipe, *, pad_multiple=None, stats=None, scrub=False,
+                     eps=MmapLiverDataset.EPS, emitter_channel=None, emitter=None, out=None,
+                     report=None):
+    """Raw G-buffers x ([B,Cin,H,W] or [Cin,H,W], fp32, on the GPU) -> the
+    recipe's channels [B,Cout,Hp,Wp] fp32 in one pass, per output sample in this
+    order: compose the term from the raw values at the (reflected) source pixel,
+    count it into the census, scrub (scrub=True: NaN -> 0, +Inf -> 1, -Inf -> 0),
+    add `emitter[b]` on `emitter_channel` only (the dc offset of the paper's
+    §3.1.1; every other channel keeps its bits), and with `stats` normalise,
+    (v - mean[c]) / (std[c] + eps) over the COMPOSED channel c. The defaults are
+    the plain composition (what the stats pass and the patch pool take);
+    pad_multiple, stats, scrub, out and report are prepare_frames's, with stats
+    of Cout entries and the census (report columns 0-2) counting the composed
+    values of an image's own pixels before the scrub. emitter: a float, B floats
+    or a device [B] fp32 tensor (read by the kernel: a captured call follows new
+    values); it goes with emitter_channel, both or neither. The recipe travels
+    in the kernel's arguments: nothing is uploaded for it. No host
+    synchronisation (host-side emitter numbers are one small upload; a device
+    tensor is used as it is)."""
+    if not isinstance(recipe, FeatureRecipe):
+        raise ValueError(f"compose_features: recipe must be a FeatureRecipe, got "
+                         f"{type(recipe).__name__}")
+    x = _frames_4d(x, "compose_features: x")
+    B, Cin, H, W = x.shape
+    recipe.check_input(Cin, "compose_features")
+    Cout = recipe.out_channels
+    Hp, Wp = padded_size(H, W, pad_multiple)
+    dev = x.device
+    per = lib.nsm_feature_blocks(Cout, Hp, Wp)
+    if per <= 0 or Cin * H * W >= 1 << 31:
+        raise ValueError(f"compose_features: unsupported frame size {Cin} x {H} x {W} -> "
+                         f"{Cout} x {Hp} x {Wp}")
+    if (emitter_channel is None) != (emitter is None):
+        raise ValueError("compose_features: emitter_channel and emitter go together, got "
+                         f"{emitter_channel!r} and {emitter!r}")
+    if emitter_channel is not None and (isinstance(emitter_channel, bool)
+                                        or not isinstance(emitter_channel, int)
+                                        or not 0 <= emitter_channel < Cout):
+        raise ValueError(f"compose_features: emitter_channel must be in [0, {Cout}), got "
+                         f"{emitter_channel!r}")
+    if out is not None:
+        _check_buffer(out, (B, Cout, Hp, Wp), torch.float32, dev, "compose_features: out")
+    if report is not None:
+        _check_buffer(report, (B, 6), torch.int32, dev, "report")
+    em = _emitter_of(emitter, B, dev) if emitter is not None else None
+    norm = _norm_of(stats, Cout, dev)    # the last check; its copy is GPU work
+    if out is None:
+        out = torch.empty((B, Cout, Hp, Wp), dtype=torch.float32, device=dev)
+    part = _census_ws(B, per, dev) if report is not None else None
+    x = x.detach().contiguous()
+    mean, std = norm if norm is not None else (None, None)
+    call("nsm_feature_compose", ptr(x), B, Cin, H, W, Hp, Wp, recipe._ctable, Cout,
+         recipe.ratio_floor, ptr(mean), ptr(std), float(eps), int(bool(scrub)),
+         -1 if emitter_channel is None else emitter_channel, ptr(em), ptr(out), ptr(part),
+         ptr(report), stream())
+    return out
+
+
 def finish_frames(out, size=None, *, quantize=True, out_u8=None, out_f32=None, report=None):
     """The network's output ([B,C,Hp,Wp] or [C,Hp,Wp], fp32, C = 1, 3 or 4) ->
     the frame as save_output writes it, in one pass: the top-left size = (H, W)
@@ -204,6 +286,16 @@ class FramePipeline(GraphedUnet):
     (a loader's copy target): `pipe.replay()` then runs the graph. `pipe.report()`
     synchronises and returns the six per-image census counts of the last frame.
 
+    With `recipe=` (a features.FeatureRecipe) the example is the RAW [B,Cin,H,W]
+    batch and compose_features takes prepare_frames's place in the graph:
+    `static_in` is [B,Cout,Hp,Wp], `stats` are those of the composed channels and
+    report columns 0-2 count the composed values. `emitter_channel=` (a composed
+    channel; it needs a recipe, FeatureRecipe.identity(C) for raw channels) adds
+    the emitter size to that channel: `pipe.emitter` is the static [B] fp32
+    device tensor the graph reads (zeros at capture) and `pipe.set_emitter(v)`
+    copies a number or B numbers into it, so the softness control of the paper's
+    §3.1.1 needs no new capture. A new recipe is a new pipeline.
+
     The defaults are the reference's inference.py: crop=False keeps the padded
     size (the reference never crops back, its PNG has the padded size; crop=True
     returns the frame's own H x W), and stats=None does not normalise. A model
@@ -218,27 +310,50 @@ class FramePipeline(GraphedUnet):
     a parameter's or buffer's version counter moved, and a RuntimeError when the
     parameters were re-allocated after the capture."""
 
-    def __init__(self, model, example, *, pad_multiple=16, stats=None, scrub=True, crop=False,
-                 static_weights=True, warmup=2):
+    def __init__(self, model, example, *, recipe=None, emitter_channel=None, pad_multiple=16,
+                 stats=None, scrub=True, crop=False, static_weights=True, warmup=2):
         if not torch.is_tensor(example) or example.dim() != 4:
             got = tuple(example.shape) if torch.is_tensor(example) else type(example).__name__
             raise ValueError(f"FramePipeline: example must be a raw [B,C,H,W] batch, got {got}")
         example = _frames_4d(example, "FramePipeline: example")
         B, C, H, W = example.shape
+        self.recipe, self.emitter_channel, self.emitter = recipe, emitter_channel, None
+        Cnet = C                                  # the channels the network sees
+        if recipe is not None:
+            if not isinstance(recipe, FeatureRecipe):
+                raise ValueError(f"FramePipeline: recipe must be a FeatureRecipe, got "
+                                 f"{type(recipe).__name__}")
+            recipe.check_input(C, "FramePipeline")
+            Cnet = recipe.out_channels
+            if emitter_channel is not None and (isinstance(emitter_channel, bool)
+                                                or not isinstance(emitter_channel, int)
+                                                or not 0 <= emitter_channel < Cnet):
+                raise ValueError(f"FramePipeline: emitter_channel must be in [0, {Cnet}), got "
+                                 f"{emitter_channel!r}")
+        elif emitter_channel is not None:
+            raise ValueError("FramePipeline: emitter_channel needs a recipe (it indexes the "
+                             "composed channels); FeatureRecipe.identity(C) is the raw case")
         Hp, Wp = padded_size(H, W, pad_multiple)
         dev = example.device
         self.shape, self.dtype = (B, C, H, W), example.dtype
         self.size = (H, W) if crop else (Hp, Wp)
-        self._prep = dict(pad_multiple=pad_multiple, stats=_norm_of(stats, C, dev), scrub=scrub)
+        self._prep = dict(pad_multiple=pad_multiple, stats=_norm_of(stats, Cnet, dev), scrub=scrub)
         self.raw = example.detach().clone(memory_format=torch.contiguous_format)
-        self.static_in = torch.empty((B, C, Hp, Wp), dtype=torch.float32, device=dev)
+        self.static_in = torch.empty((B, Cnet, Hp, Wp), dtype=torch.float32, device=dev)
+        if emitter_channel is not None:
+            self.emitter = torch.zeros(B, dtype=torch.float32, device=dev)
         self.shadow = self._report = None
         self._capture(model, warmup, static_weights)
 
     def _body(self):
         B = self.shape[0]
         self._report = torch.empty((B, 6), dtype=torch.int32, device=self.raw.device)
-        prepare_frames(self.raw, out=self.static_in, report=self._report, **self._prep)
+        if self.recipe is None:
+            prepare_frames(self.raw, out=self.static_in, report=self._report, **self._prep)
+        else:
+            compose_features(self.raw, self.recipe, out=self.static_in, report=self._report,
+                             emitter_channel=self.emitter_channel, emitter=self.emitter,
+                             **self._prep)
         o = self.model(self.static_in)      # fp32 in every compute dtype (finish_frames checks)
         self.shadow = torch.empty((B, o.shape[1]) + self.size, dtype=torch.float32, device=o.device)
         return finish_frames(o, self.size, out_f32=self.shadow, report=self._report)
@@ -254,6 +369,22 @@ class FramePipeline(GraphedUnet):
         self.raw.copy_(x)
         self.graph.replay()
         return self.static_out
+
+    def set_emitter(self, values):
+        """Copy the emitter size (a number, or one per image) into `pipe.emitter` on
+        the current stream; the next replay adds it to the emitter channel."""
+        if self.emitter is None:
+            raise ValueError("FramePipeline: set_emitter needs emitter_channel= at construction")
+        B = self.shape[0]
+        try:
+            v = torch.as_tensor(values, dtype=torch.float32).reshape(-1)
+        except (TypeError, ValueError, RuntimeError):
+            v = None
+        if v is None or v.numel() not in (1, B):
+            raise ValueError(f"FramePipeline: set_emitter takes a number or {B} numbers, got "
+                             f"{values!r}")
+        self.emitter.copy_(v.expand(B))
+        return self.emitter
 
     def report(self):
         """{key: [count per image]} of the last frame (REPORT_KEYS). Waits for it."""

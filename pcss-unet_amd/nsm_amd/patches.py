@@ -189,15 +189,24 @@ class PatchSampler:
             self._words = torch.tensor([_as_i64(seed), 0], dtype=torch.int64).to(dev)
 
     @classmethod
-    def from_dir(cls, data_dir, split="train", device="cuda", stats_dir=None, **kw):
+    def from_dir(cls, data_dir, split="train", device="cuda", stats_dir=None, recipe=None, **kw):
         """Upload {split}_inputs.npy / {split}_labels.npy once (through the native
         loader, which converts f64 labels on the way) and sample from them.
         Stats as FrameLoader takes them: `stats=`, else train_stats.json under
-        stats_dir or data_dir; neither: no normalisation."""
+        stats_dir or data_dir; neither: no normalisation. recipe (a
+        features.FeatureRecipe): each uploaded chunk is composed on the device
+        (frames.compose_features, no scrub) and the pool holds the recipe's
+        channels; stats, hflip_sign, vflip_sign and emitter_channel then index
+        the composed channels."""
         dev = torch.device(device)
         shape = np.load(os.path.join(data_dir, f"{split}_inputs.npy"), mmap_mode="r").shape
-        N, C, H, W = (int(v) for v in shape)
-        chunk = max(1, min(N, UPLOAD_BYTES // (4 * C * H * W)))
+        N, Craw, H, W = (int(v) for v in shape)
+        C = Craw
+        if recipe is not None:
+            from .frames import compose_features
+            recipe.check_input(Craw, "patch sampler")
+            C = recipe.out_channels
+        chunk = max(1, min(N, UPLOAD_BYTES // (4 * Craw * H * W)))
         loader = FrameLoader(data_dir, split, batch=chunk, device=dev, apply_normalization=False)
         inputs = torch.empty((N, C, H, W), dtype=torch.float32, device=dev)
         labels = torch.empty((N, 1, H, W), dtype=torch.float32, device=dev)
@@ -205,7 +214,10 @@ class PatchSampler:
         try:
             for _ in range(len(loader)):
                 x, y = loader.next()
-                inputs[at:at + x.shape[0]].copy_(x.detach())
+                if recipe is None:
+                    inputs[at:at + x.shape[0]].copy_(x.detach())
+                else:
+                    compose_features(x.detach(), recipe, out=inputs[at:at + x.shape[0]])
                 labels[at:at + x.shape[0]].copy_(y)
                 at += x.shape[0]
         finally:

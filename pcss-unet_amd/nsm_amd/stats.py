@@ -177,7 +177,7 @@ def save_stats(stats_dir, means, stds):
 
 
 def dataset_stats(data_dir, split="train", batch=8, device="cuda", world=1, rank=0, save=True,
-                  nonfinite="raise", per_frame=False):
+                  nonfinite="raise", per_frame=False, recipe=None):
     """Statistics of `{split}_inputs.npy` under data_dir, streamed raw through
     FrameLoader (this rank's shard, the short last batch included). Returns the
     StatsResult, and with per_frame=True also the [N,C,6] fp64 table of every
@@ -187,8 +187,12 @@ def dataset_stats(data_dir, split="train", batch=8, device="cuda", world=1, rank
     it needs the whole split (world == 1): merge shards with ChannelStats.merge
     and write with save_stats. nonfinite="raise" raises ValueError naming the
     channels that hold NaN or Inf and how many; "skip" accepts them (they are
-    left out of the figures either way)."""
+    left out of the figures either way). recipe (a features.FeatureRecipe): every
+    uploaded batch is composed on the device (frames.compose_features, no scrub)
+    before it is folded in, so the figures, and the file, are those of the
+    recipe's channels: what a model trained on them normalises with."""
     from .data import FrameLoader
+    from .frames import compose_features
     if nonfinite not in _NONFINITE:
         raise ValueError(f"dataset stats: nonfinite must be one of {_NONFINITE}, got {nonfinite!r}")
     if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
@@ -203,11 +207,16 @@ def dataset_stats(data_dir, split="train", batch=8, device="cuda", world=1, rank
     loader = FrameLoader(data_dir, split=split, batch=batch, device=dev, world=world, rank=rank,
                          apply_normalization=False)
     try:
-        acc = ChannelStats(loader.C)
+        if recipe is not None:
+            recipe.check_input(loader.C, "dataset stats")
+        acc = ChannelStats(loader.C if recipe is None else recipe.out_channels)
         tables = []
         for _ in range(len(loader)):
             x, _ = loader.next()
-            t = acc.update(x.detach(), per_frame=per_frame)
+            x = x.detach()
+            if recipe is not None:
+                x = compose_features(x, recipe)
+            t = acc.update(x, per_frame=per_frame)
             if per_frame:
                 tables.append(t)
         res = acc.compute()
