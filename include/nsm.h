@@ -1293,6 +1293,44 @@ int nsm_feature_compose(const float* x, int B, int Cin, int H, int W, int Hp, in
                         const float* emitter, float* out, uint32_t* partial, int32_t* report,
                         void* stream);
 
+/* ---- learned feature extraction (csrc/nsm_extract.hip) ---------------
+ * The paper's feature-extraction network (§3.2): a per-pixel 2-layer MLP, two 1x1
+ * convolutions around a LeakyReLU. x [B][Cin][H][W] fp32 -> y [B][Cout][H][W]
+ * fp32; w1 [Hd][Cin], b1 [Hd], w2 [Cout][Hd], b2 [Cout] are the memory of
+ * nn.Conv2d(.., 1).weight / .bias as it stands (device pointers, read at launch
+ * time by the kernels: a captured call follows new values).
+ * nsm_extract_fwd: per pixel, each dot product one fmaf chain from the bias in
+ *   ascending index order:
+ *     pre[j] = b1[j] + sum_i w1[j][i] x[i];  h[j] = pre[j] > 0 ? pre[j] : pre[j] * slope;
+ *     y[c] = b2[c] + sum_j w2[c][j] h[j].
+ * nsm_extract_bwd: from x, dy [B][Cout][H][W] and the parameters (pre and h are
+ *   recomputed by the forward's chain; nothing else is kept from the forward):
+ *     dh[j] = (pre[j] > 0 ? 1 : slope) * sum_c w2[c][j] dy[c];
+ *     dx[i] = sum_j w1[j][i] dh[j]        (dx NULL: not computed, nothing written);
+ *     dw1 = sum dh (x) x, db1 = sum dh, dw2 = sum dy (x) h, db2 = sum dy over all
+ *     B*H*W pixels, written (not accumulated) in the parameters' layouts.
+ *   The sums use no atomics: block partials go to ws and a second launch merges
+ *   them in a fixed order, so the result is a pure function of the arguments, bit
+ *   for bit on every run, stream and graph replay. ws holds nsm_extract_bwd_ws
+ *   bytes (a host function: the grid is capped, so the size does not grow with
+ *   the image beyond the cap).
+ * nsm_extract_bwd_plan: plan[0..5] = blocks of the backward grid, tiles, units of
+ *   a tile, pixels of a unit (4 consecutive columns of a row), the grid's cap,
+ *   floats of one block's partial. Block k folds the tiles k, k + grid, ...
+ * Limits (NSM_E_ARG before any launch otherwise): 1 <= Cin <= 32, 1 <= Hd <= 32,
+ *   1 <= Cout <= 16, max(Cin, Cout)*H*W < 2^31, B*H*ceil(W/4) < 2^31, pointers
+ *   4-byte aligned (16-byte accesses are used wherever an address allows). No
+ *   allocation, no host synchronisation; capturable. */
+int nsm_extract_fwd(const float* x, int B, int Cin, int H, int W, const float* w1,
+                    const float* b1, int Hd, const float* w2, const float* b2, int Cout,
+                    float slope, float* y, void* stream);
+size_t nsm_extract_bwd_ws(int B, int Cin, int H, int W, int Hd, int Cout);
+int nsm_extract_bwd_plan(int B, int Cin, int H, int W, int Hd, int Cout, int32_t* plan);
+int nsm_extract_bwd(const float* x, const float* dy, int B, int Cin, int H, int W,
+                    const float* w1, const float* b1, int Hd, const float* w2, const float* b2,
+                    int Cout, float slope, float* dw1, float* db1, float* dw2, float* db2,
+                    float* dx, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@ from .optim import (FlatAdam, FlatAdamW, FlatSGD, allreduce_grads, flat_grad,  #
 from .grad_scaler import GradScaler  # noqa: F401
 from .infer import GraphedUnet  # noqa: F401
 from .features import FeatureRecipe  # noqa: F401
+from .extract import ExtractedUnet, FeatureExtractor  # noqa: F401
 from .frames import (FramePipeline, compose_features, finish_frames,  # noqa: F401
                      prepare_frames)
 from .patches import PatchSampler, patch_draws  # noqa: F401

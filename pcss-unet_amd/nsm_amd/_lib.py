@@ -178,6 +178,10 @@ _SIGS = {
     "nsm_patch_advance": (I, [P, P]),
     "nsm_feature_blocks": (I, [I, I, I]),
     "nsm_feature_compose": (I, [P, I, I, I, I, I, I, P, I, F, P, P, F, I, I, P, P, P, P, P]),
+    "nsm_extract_fwd": (I, [P, I, I, I, I, P, P, I, P, P, I, F, P, P]),
+    "nsm_extract_bwd_ws": (Z, [I, I, I, I, I, I]),
+    "nsm_extract_bwd_plan": (I, [I, I, I, I, I, I, P]),
+    "nsm_extract_bwd": (I, [P, P, I, I, I, I, P, P, I, P, P, I, F, P, P, P, P, P, P, P]),
     "nsm_pack_conv_weight_bf16": (I, [P, I, I, I, I, I, I, P, P]),
     "nsm_conv_fwd_bf16": (I, [P, I, I, I, I, I, P, P, I, I, P, I, P, P, P, F, P, P]),
     "nsm_conv_wgrad_bf16_ws": (Z, [I, I, I, I, I, I]),

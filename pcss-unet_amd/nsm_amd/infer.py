@@ -49,7 +49,9 @@ class GraphedUnet:
         self.model = model
         self.was_training = model.training
         model.eval()
-        self.frozen = FrozenWeights(model) if static_weights else None
+        # an extract.ExtractedUnet: the layouts kept are its U-Net's; the extractor
+        # reads its live parameters at their fixed addresses on every replay
+        self.frozen = FrozenWeights(getattr(model, "unet", model)) if static_weights else None
         side = torch.cuda.Stream(device=self.static_in.device)
         side.wait_stream(torch.cuda.current_stream())
         if self.frozen is not None:

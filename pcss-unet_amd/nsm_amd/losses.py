@@ -792,7 +792,8 @@ class EnhancedCustomLoss(nn.Module):
         # the weights are those of the forward that produced `output`: the
         # perturbed forwards keep its prepared layouts (bitwise the same results)
         from .unet import reuse_prepared_weights
-        with torch.no_grad(), reuse_prepared_weights(model):
+        # (an extract.ExtractedUnet prepares its U-Net's layouts: the key is that module)
+        with torch.no_grad(), reuse_prepared_weights(getattr(model, "unet", model)):
             pouts = [model(p) for p in pins]
         # a differentiated VGG term stays its own node: its value joins below
         total, l1, pert = _PertLossFn.apply(output, target, self.alpha, self.perturb_weight,
