@@ -35,7 +35,8 @@ extern "C" {
 
 /* storage type of activation / activation-gradient buffers (void* args):
  * every elementwise entry point below that takes `int dtype` reads and writes
- * its NHWC tensors in that type and computes in fp32 */
+ * its NHWC tensors in that type and computes in fp32. Any other code is
+ * NSM_E_ARG: the entry launches nothing. */
 #define NSM_F32 0
 #define NSM_BF16 1
 #define NSM_F16 2  /* IEEE half storage (the fp16-autocast mode) */
@@ -1001,7 +1002,8 @@ int nsm_sgd_tail_dev(float* p, const float* g, float* buf, const int* blk_seg,
                      double weight_decay, void* stream);
 
 /* ---- drop-in surface helpers ---------------------------------------------------
- * NCHW fp32 <-> NHWC [B*H*W][cp] (dtype NSM_F32 / NSM_BF16) for a standalone
+ * NCHW fp32 <-> NHWC [B*H*W][cp] (dtype NSM_F32 / NSM_BF16 / NSM_F16; another
+ * code is NSM_E_ARG) for a standalone
  * DoubleConv call (Unetmodel.py:32-33); channels C..cp-1 are written as 0.
  * nsm_range_flag: flag[0] = 1 if any o[i] is outside [lo, hi] or NaN (the
  * `assert output.min() >= 0 and output.max() <= 1` of customLoss.py:131 /
@@ -1055,7 +1057,7 @@ int nsm_conv_fwd_bf16(const void* x, int ldx, int B, int H, int W, int cin_p, co
  * (the scale source of nsm_wino_dual_bn_f16).
  * Replaces ConvolutionBackward(conv.4) + BatchNorm/LeakyReLU/Dropout2d
  * backward of conv.1-3 (autograd of Unetmodel.py:21-26). dtype NSM_F32 | NSM_BF16 |
- * NSM_F16 (the 16-bit ones: dy2, w2d, y1, out in it). */
+ * NSM_F16 (the 16-bit ones: dy2, w2d, y1, out in it); another code is NSM_E_ARG. */
 int nsm_conv1x1_dgrad_bnbwd(const void* dy2, int lddy2, int B, int H, int W, int cop,
                             const void* w2d, int cip, const void* y1, int ldy1,
                             const float* scale, const float* shift, const float* mean,
@@ -1072,7 +1074,7 @@ int nsm_conv1x1_bnbwd_chunks(int B, int H, int W, int cip, int cop, int dtype);
  * act_shift, slope) (+ res: the decoder's additive skip, :125-137), round =
  * the storage dtype's (the value the unfused conv -> bn_act pair stores in
  * between); act_scale / act_shift from nsm_bn_finalize_eval. dtype NSM_F32 |
- * NSM_BF16 | NSM_F16 (x, wpk, y, res in it). */
+ * NSM_BF16 | NSM_F16 (x, wpk, y, res in it); another code is NSM_E_ARG. */
 int nsm_conv_fwd_act(const void* x, int ldx, int B, int H, int W, int cin_p, const void* wpk,
                      const float* bias, int cout_p, int ksize, void* y, int ldy,
                      const float* act_scale, const float* act_shift, float slope, const void* res,

@@ -7,6 +7,7 @@
 #include <stddef.h>
 #include <stdlib.h>
 #include <string>
+#include <type_traits>
 
 #include "../../include/nsm.h"
 
@@ -246,6 +247,30 @@ __device__ __forceinline__ void st8(f16_t* p, F8 v) {
 __device__ __forceinline__ float ld1(const f16_t* p) { return h_lo((uint32_t)p->bits); }
 __device__ __forceinline__ void st1(f16_t* p, float v) {
   p->bits = (unsigned short)(pack_hh(v, 0.f) & 0xFFFFu);
+}
+
+// ---- storage-type dispatch (host) -------------------------------------------
+// The one place a dtype code becomes an element type: f(TypeTag<T>{}) -> int
+// for T = float | bf16_t | f16_t, and f's return code is passed on, so an
+// NSM_CHECK_ARG / NSM_LAUNCH_CHECK inside f fails the entry. Any other code is
+// NSM_E_ARG (`what`: the entry's name) and f is not called.
+template <typename T>
+struct TypeTag {
+  using type = T;
+};
+template <typename F>
+inline int for_dtype(int dtype, const char* what, F&& f) {
+  switch (dtype) {
+    case NSM_BF16: return f(TypeTag<bf16_t>{});
+    case NSM_F16: return f(TypeTag<f16_t>{});
+    case NSM_F32: return f(TypeTag<float>{});
+  }
+  return fail(NSM_E_ARG, "%s: dtype code %d is not NSM_F32, NSM_BF16 or NSM_F16", what, dtype);
+}
+// a run-time bool as a template argument: f(std::true_type{} / std::false_type{}) -> int
+template <typename F>
+inline int for_bool(bool v, F&& f) {
+  return v ? f(std::true_type{}) : f(std::false_type{});
 }
 
 __device__ __forceinline__ void split4h(f32x4 v, float s, u32x2& h, u32x2& l) {

@@ -67,17 +67,16 @@ extern "C" int nsm_conv_fwd_act(const void* x, int ldx, int B, int H, int W, int
                                 const void* wpk, const float* bias, int cout_p, int ksize, void* y,
                                 int ldy, const float* act_scale, const float* act_shift,
                                 float slope, const void* res, int ldres, int dtype, void* stream) {
-  hipStream_t s = as_stream(stream);
-  if (dtype == NSM_BF16)
-    return nsm_bf::s16_conv_fwd_act(x, ldx, B, H, W, cin_p, wpk, bias, cout_p, ksize, y, ldy,
-                                 act_scale, act_shift, slope, res, ldres, s);
-  if (dtype == NSM_F16)
-    return conv_fwd_act_f16(x, ldx, B, H, W, cin_p, wpk, bias, cout_p, ksize, y, ldy, act_scale,
-                            act_shift, slope, res, ldres, s);
-  NSM_CHECK_ARG(dtype == NSM_F32, "conv_fwd_act: dtype %d", dtype);
-  return conv_fwd_act_f32((const float*)x, ldx, B, H, W, cin_p, (const float*)wpk, bias, cout_p,
-                          ksize, (float*)y, ldy, act_scale, act_shift, slope, (const float*)res,
-                          ldres, s);
+  return for_dtype(dtype, "conv_fwd_act", [&, s = as_stream(stream)](auto t) {
+    using T = typename decltype(t)::type;
+    if constexpr (std::is_same<T, float>::value)
+      return conv_fwd_act_f32((const T*)x, ldx, B, H, W, cin_p, (const T*)wpk, bias, cout_p, ksize,
+                              (T*)y, ldy, act_scale, act_shift, slope, (const T*)res, ldres, s);
+    else  // the two 16-bit formats share a signature
+      return (std::is_same<T, bf16_t>::value ? nsm_bf::s16_conv_fwd_act : conv_fwd_act_f16)(
+          x, ldx, B, H, W, cin_p, wpk, bias, cout_p, ksize, y, ldy, act_scale, act_shift, slope,
+          res, ldres, s);
+  });
 }
 
 // ---- 1x1 input gradient with the BN backward in its epilogue (EpiBnBwd) ----
@@ -96,8 +95,6 @@ extern "C" int nsm_conv1x1_dgrad_bnbwd(const void* dy2, int lddy2, int B, int H,
                                        int ldo, int dtype, const uint32_t* amax_dy2,
                                        const uint32_t* amax_w, uint32_t* amax_out, void* stream) {
   NSM_CHECK_ARG(dy2 && w2d && y1 && scale && shift && mean, "conv1x1_dgrad_bnbwd: null pointer");
-  NSM_CHECK_ARG(dtype == NSM_F32 || dtype == NSM_BF16 || dtype == NSM_F16,
-                "conv1x1_dgrad_bnbwd: dtype %d", dtype);
   NSM_CHECK_ARG(mode >= 0 && mode <= 2, "conv1x1_dgrad_bnbwd: mode %d", mode);
   NSM_CHECK_ARG(mode == 2 || (partial && invstd), "conv1x1_dgrad_bnbwd: modes 0/1 need partials");
   NSM_CHECK_ARG(mode == 0 || out, "conv1x1_dgrad_bnbwd: modes 1/2 need an output");
@@ -118,11 +115,14 @@ extern "C" int nsm_conv1x1_dgrad_bnbwd(const void* dy2, int lddy2, int B, int H,
   // 16-bit modes 0/1: amax_out receives max|scale * dz|, the k1 term of the dY1
   // bound nsm_bn_bwd_finalize derives (the lazy-dY1 dual transform's scale)
   if (dtype != NSM_F32 && mode != 2) ep.k1dz = amax_out;
-  hipStream_t s = as_stream(stream);
-  if (dtype == NSM_BF16)
-    return nsm_bf::s16_conv1x1_dgrad_bnbwd(dy2, lddy2, B, H, W, cop, w2d, cip, ep, s);
-  if (dtype == NSM_F16)
-    return conv1x1_dgrad_bnbwd_f16(dy2, lddy2, B, H, W, cop, w2d, cip, ep, s);
-  return conv1x1_dgrad_bnbwd_f32((const float*)dy2, lddy2, B, H, W, cop, (const float*)w2d, cip, ep,
-                                 amax_dy2, amax_w, s);
+  return for_dtype(dtype, "conv1x1_dgrad_bnbwd", [&, s = as_stream(stream)](auto t) {
+    using T = typename decltype(t)::type;
+    constexpr bool bf = std::is_same<T, bf16_t>::value;
+    if constexpr (std::is_same<T, float>::value)
+      return conv1x1_dgrad_bnbwd_f32((const T*)dy2, lddy2, B, H, W, cop, (const T*)w2d, cip, ep,
+                                     amax_dy2, amax_w, s);
+    else
+      return (bf ? nsm_bf::s16_conv1x1_dgrad_bnbwd : conv1x1_dgrad_bnbwd_f16)(
+          dy2, lddy2, B, H, W, cop, w2d, cip, ep, s);
+  });
 }

@@ -196,17 +196,12 @@ extern "C" int nsm_nchw_to_nhwc(const float* x, int B, int C, int H, int W, void
   const int HW = H * W;
   dim3 grid((HW + LT_P - 1) / LT_P, (cp + LT_C - 1) / LT_C, B);
   hipStream_t s = as_stream(stream);
-  if (dtype == NSM_BF16)
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel<bf16_t>, grid, dim3(256), 0, s, x, C, HW, cp,
-                       (bf16_t*)y, ldy);
-  else if (dtype == NSM_F16)
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel<f16_t>, grid, dim3(256), 0, s, x, C, HW, cp,
-                       (f16_t*)y, ldy);
-  else
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, grid, dim3(256), 0, s, x, C, HW, cp, (float*)y,
-                       ldy);
-  NSM_LAUNCH_CHECK("nchw_to_nhwc");
-  return 0;
+  return for_dtype(dtype, "nchw_to_nhwc", [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel<T>, grid, dim3(256), 0, s, x, C, HW, cp, (T*)y, ldy);
+    NSM_LAUNCH_CHECK("nchw_to_nhwc");
+    return 0;
+  });
 }
 
 extern "C" int nsm_nhwc_to_nchw(const void* z, int ldz, int B, int C, int H, int W, float* x,
@@ -215,17 +210,12 @@ extern "C" int nsm_nhwc_to_nchw(const void* z, int ldz, int B, int C, int H, int
   const int HW = H * W;
   dim3 grid((HW + LT_P - 1) / LT_P, (C + LT_C - 1) / LT_C, B);
   hipStream_t s = as_stream(stream);
-  if (dtype == NSM_BF16)
-    hipLaunchKernelGGL(nhwc_to_nchw_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)z, ldz,
-                       C, HW, x);
-  else if (dtype == NSM_F16)
-    hipLaunchKernelGGL(nhwc_to_nchw_kernel<f16_t>, grid, dim3(256), 0, s, (const f16_t*)z, ldz,
-                       C, HW, x);
-  else
-    hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, grid, dim3(256), 0, s, (const float*)z, ldz, C,
-                       HW, x);
-  NSM_LAUNCH_CHECK("nhwc_to_nchw");
-  return 0;
+  return for_dtype(dtype, "nhwc_to_nchw", [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(nhwc_to_nchw_kernel<T>, grid, dim3(256), 0, s, (const T*)z, ldz, C, HW, x);
+    NSM_LAUNCH_CHECK("nhwc_to_nchw");
+    return 0;
+  });
 }
 
 extern "C" int nsm_range_flag(const float* o, int64_t n, float lo, float hi, int* flag,

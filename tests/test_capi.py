@@ -5,6 +5,7 @@ import os
 import re
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "nsm.h")
@@ -38,6 +39,37 @@ def test_error_path_without_gpu_work():
                             0.2, None)
     assert rc == 1
     assert "null" in L.last_error()
+
+
+P1 = 4096    # a non-null pointer that is never dereferenced: the checks come first
+
+# (entry, its name in messages, index of the dtype argument, otherwise valid arguments):
+# one entry per source that turns a dtype code into an element type (nsm_vgg.hip
+# is fp32 only and has none), plus a resample entry whose whole body is typed
+BAD_DTYPE = [
+    ("nsm_bn_stats", "bn_stats", 6, [P1, 8, 64, 8, P1, None, 7, None]),
+    ("nsm_avgpool2_fwd", "avgpool2_fwd", 6, [P1, 1, 4, 4, 8, P1, 7, None]),
+    ("nsm_resize_bwd", "resize_bwd", 8, [P1, 1, 4, 4, 8, P1, 8, 8, 7, None]),
+    ("nsm_head_fwd", "head_fwd", 8, [P1, 16, 1, 4, 4, P1, P1, P1, 7, None]),
+    ("nsm_nchw_to_nhwc", "nchw_to_nhwc", 8, [P1, 1, 3, 4, 4, P1, 8, 8, 7, None]),
+    ("nsm_conv_fwd_act", "conv_fwd_act", 17,
+     [P1, 32, 1, 8, 8, 32, P1, P1, 32, 3, P1, 32, P1, P1, 0.2, None, 0, 7, None]),
+]
+
+
+@pytest.mark.parametrize("entry,name,at,args", BAD_DTYPE, ids=[c[0] for c in BAD_DTYPE])
+def test_unknown_dtype_code_is_an_argument_error(entry, name, at, args):
+    """A dtype code other than NSM_F32 / NSM_BF16 / NSM_F16 is NSM_E_ARG (1) with
+    a message naming the entry and the code; nothing is launched (no GPU is
+    needed, and the pointers are never read)."""
+    import nsm_amd._lib as L
+    args = list(args)
+    assert args[at] == 7
+    if entry == "nsm_bn_stats":
+        args[5] = L.lib.nsm_reduce_chunks(args[2], args[3])
+    assert getattr(L.lib, entry)(*args) == 1
+    msg = L.last_error()
+    assert name in msg and "dtype code 7" in msg, msg
 
 
 def test_wgrad_workspace_plan():

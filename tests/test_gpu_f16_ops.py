@@ -8,6 +8,9 @@ overflow to +-Inf), each against the float64 restatement of f16_util.py under
 its element-wise worst-case bounds (stated there; none measured on the
 kernels). The worst err / bound of every family goes to parity_margins.json as
 f16_ops.<family>."""
+import os
+import subprocess
+import sys
 import types
 
 import pytest
@@ -23,6 +26,10 @@ from util import record_margin
 pytestmark = pytest.mark.gpu
 torch.set_num_threads(16)
 FMTS = ["f16", "bf16"]
+# NSM_RESIZE_SEP=2 (read once per process): the separable resize forms in 16-bit
+# storage too; test_separable_forms_in_a_child_process runs the resize tests so
+SEP16 = os.environ.get("NSM_RESIZE_SEP") == "2"
+MARGIN_KEY = "f16_ops_sep." if SEP16 else "f16_ops."
 
 
 @pytest.fixture(scope="module")
@@ -39,7 +46,7 @@ def margin(family, case_id, ratio):
     """Keep the worst error / bound of a kernel family in parity_margins.json."""
     if ratio >= _WORST.get(family, (-1.0, None))[0]:
         _WORST[family] = (float(ratio), case_id)
-        record_margin("f16_ops." + family, worst_err_over_bound=float(ratio), case=case_id)
+        record_margin(MARGIN_KEY + family, worst_err_over_bound=float(ratio), case=case_id)
 
 
 def check(family, case_id, got, ref, bound, keep=None):
@@ -329,7 +336,8 @@ def test_bn_partials_and_train(ops, device, M, C, fmt):
         assert (bn.running_var.cpu().double() - (0.9 + 0.1 * var_u)).abs().max() <= 1e-4
 
 
-ACT_SHAPES = [(2, 6, 5, 64), (1, 9, 7, 128), (2, 33, 35, 32)]
+# C = 40: C / 8 = 5 does not divide 256, so pix_launch picks a 255-thread block
+ACT_SHAPES = [(2, 6, 5, 64), (1, 9, 7, 128), (2, 33, 35, 32), (2, 5, 7, 40)]
 
 
 @pytest.mark.parametrize("fmt", FMTS)
@@ -351,7 +359,7 @@ def test_bn_act(ops, device, B, H, W, C, fmt):
 
 
 @pytest.mark.parametrize("fmt", FMTS)
-@pytest.mark.parametrize("B,H,W,C", [(2, 16, 18, 64), (1, 9, 7, 128), (2, 5, 9, 512)])
+@pytest.mark.parametrize("B,H,W,C", [(2, 16, 18, 64), (1, 9, 7, 128), (2, 5, 9, 512), (2, 5, 7, 40)])
 def test_bn_act_pool(ops, device, B, H, W, C, fmt):
     """z as bn_act; the pooled output is the mean of the stored z: its bound
     carries the propagated bound of z."""
@@ -448,6 +456,23 @@ def test_resize_act(ops, device, B, H, W, C, fmt):
         bound = U.elem_bound(ref, U.resample(z, wy, wx, absval=True), fam, fmt,
                              extra=U.resample(bz, wy, wx, absval=True))
         check(f"{fam}_act_{fmt}", sid(B, H, W, C), from_dev(ops, fmt, device, got, B, ho, wo), ref, bound)
+
+
+def test_separable_forms_in_a_child_process():
+    """By default only fp32 takes the separable resize kernels; the knob that
+    gives them to 16-bit storage is read once per process. A child process
+    with NSM_RESIZE_SEP=2 runs the resize tests of this file (resize, the
+    composite, the Lazy forms, the fused BN reduction; f16 and bf16) against
+    their own float64 references and bounds, which hold for either form."""
+    if SEP16:
+        return                                   # the child itself
+    tests = ["test_resize", "test_up2_resize", "test_resize_act", "test_grad_producer_bnred"]
+    env = dict(os.environ, NSM_RESIZE_SEP="2")
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-p", "no:cacheprovider"]
+                       + [f"{__file__}::{t}" for t in tests], env=env, capture_output=True,
+                       text=True, timeout=600, cwd=os.path.dirname(os.path.dirname(__file__)))
+    print(r.stdout[-3000:], r.stderr[-2000:])
+    assert r.returncode == 0 and " passed" in r.stdout and "failed" not in r.stdout
 
 
 def bn_bwd_ref(g_, y, v, mask):

@@ -249,7 +249,16 @@ def test_bn_train_stats(ops, device, M, C):
 
 def test_bn_act_and_bwd(ops, device):
     """bn_train -> bn_act -> bn_bwd against autograd of F.batch_norm+lrelu*mask."""
-    B, C, H, W = 2, 64, 6, 5
+    _bn_act_and_bwd_case(ops, device, 2, 64, 6, 5)
+
+
+def test_bn_act_and_bwd_odd_block(ops, device):
+    """C = 40: C / 8 = 5 does not divide 256, so the pixel-row kernels run in
+    255-thread blocks; test_bn_act_and_bwd's reference and bounds."""
+    _bn_act_and_bwd_case(ops, device, 2, 40, 5, 7)
+
+
+def _bn_act_and_bwd_case(ops, device, B, C, H, W):
     g = torch.Generator().manual_seed(5)
     y = (torch.randn(B, C, H, W, generator=g) * 2 + 1).requires_grad_(True)
     gamma = (torch.rand(C, generator=g) + 0.5).requires_grad_(True)
@@ -340,9 +349,22 @@ def test_conv1x1_dgrad_bn_bwd(ops, device, B, H, W, cip, cop, drop, recompute, d
 
 @pytest.mark.parametrize("Hi,Wi,Ho,Wo", [(4, 5, 8, 10), (8, 10, 4, 5), (2, 4, 4, 8), (4, 8, 5, 9),
                                          (67, 120, 134, 240), (134, 240, 135, 240), (1, 1, 2, 2),
-                                         (5, 5, 5, 5), (64, 64, 32, 32)])
+                                         (5, 5, 5, 5), (64, 64, 32, 32),
+                                         # fp32 forms no narrower shape takes: rows too wide for a
+                                         # separable plan (row-blocked backward), and past the LDS
+                                         # tables of that one (the gather)
+                                         (2, 1100, 4, 2200), (2, 2050, 4, 4100)])
 def test_resize(ops, device, Hi, Wi, Ho, Wo):
-    B, C = 2, 8
+    _resize_case(ops, device, 2, 8, Hi, Wi, Ho, Wo)
+
+
+def test_resize_scalar_channels(ops, device):
+    """C % 8 != 0 (the odd-size input guard runs on [B*C][H][W][1]): the scalar
+    kernels in fp32, to test_resize's reference and bounds."""
+    _resize_case(ops, device, 6, 1, 5, 7, 4, 6)
+
+
+def _resize_case(ops, device, B, C, Hi, Wi, Ho, Wo):
     g = torch.Generator().manual_seed(Hi * Wo)
     x = torch.randn(B, C, Hi, Wi, generator=g, requires_grad=True)
     ref = F.interpolate(x, size=(Ho, Wo), mode="bilinear", align_corners=True)
@@ -355,7 +377,12 @@ def test_resize(ops, device, Hi, Wi, Ho, Wo):
 
 
 @pytest.mark.parametrize("h,w,th,tw", [(8, 10, 8, 10), (32, 32, 32, 32), (2, 4, 5, 9), (67, 120, 135, 240),
-                                       (5, 7, 5, 7)])
+                                       (5, 7, 5, 7),
+                                       # fp32 forms the shapes above do not take: the per-element
+                                       # forward (second step shrinks), the row-blocked forward and
+                                       # backward (no separable plan), the gathers (rows > 2048)
+                                       (8, 10, 7, 9), (2, 1100, 3, 1500), (2, 1100, 4, 2200),
+                                       (2, 2050, 4, 4100)])
 def test_up2_resize_composite(ops, device, h, w, th, tw):
     """fused up x2 + _upsample_and_match == the two-step reference path."""
     B, C = 2, 8
@@ -491,7 +518,10 @@ def test_adamw_clip(device):
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 @pytest.mark.parametrize("kind,B,h,w,C", [("pool", 2, 16, 18, 64), ("pool", 3, 9, 7, 1024),
                                           ("resize", 2, 8, 10, 128), ("resize", 1, 33, 20, 512),
-                                          ("up2", 2, 16, 16, 64), ("up2", 1, 67, 120, 32)])
+                                          ("up2", 2, 16, 16, 64), ("up2", 1, 67, 120, 32),
+                                          # too wide for a separable plan: the row-blocked
+                                          # kernels with the fused reduction in fp32 too
+                                          ("resize", 1, 2, 1100, 32), ("up2", 1, 2, 1100, 32)])
 def test_grad_producer_bn_reduce(ops, device, kind, B, h, w, C, dtype):
     """The pooling / resize backward with the next BN's backward reduction fused
     (bnred=): the same gradient, and bn_bwd on its partials == bn_bwd with its
@@ -588,7 +618,7 @@ def test_wino_dual_input(ops, device, B, H, W, ci, co, tile):
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
-@pytest.mark.parametrize("B,H,W,C", [(2, 16, 18, 64), (1, 9, 7, 128), (2, 5, 9, 512)])
+@pytest.mark.parametrize("B,H,W,C", [(2, 16, 18, 64), (1, 9, 7, 128), (2, 5, 9, 512), (2, 5, 7, 40)])
 def test_bn_act_pool_and_lazy_resize(ops, device, B, H, W, C, dtype):
     """bn_act_pool == bn_act then avgpool2 (bitwise); resize / up2_resize of a
     Lazy block output == bn_act(+res) then the resize (bitwise)."""
@@ -609,4 +639,21 @@ def test_bn_act_pool_and_lazy_resize(ops, device, B, H, W, C, dtype):
                        ops.resize_act(lazy, B, H, W, 2 * H, 2 * W, 0.2))
     th, tw = 2 * H - 1, 2 * W - 1
     a = ops.up2_resize_act(lazy, B, H, W, th, tw, 0.2)
+    assert a is not None and torch.equal(ops.up2_resize(zr, B, H, W, th, tw), a)
+
+
+def test_lazy_up2_resize_row_blocked_f32(ops, device):
+    """A 1100-pixel source row has no separable plan in fp32 (8 channels of it
+    exceed the forward's LDS row), so up2_resize_act and up2_resize both take
+    the row-blocked kernel: the Lazy form == bn_act(+res) then up2_resize
+    (bitwise), as in test_bn_act_pool_and_lazy_resize."""
+    B, H, W, C, th, tw = 1, 2, 1100, 8, 3, 1500
+    g = torch.Generator().manual_seed(H * W + C)
+    y = (torch.randn(B * H * W, C, generator=g) * 2).to(device)
+    res = torch.randn(B * H * W, C, generator=g).to(device)
+    st = ops.BNState(C, device)
+    st.scale.copy_(torch.rand(C, generator=g) + 0.5)
+    st.shift.copy_(torch.randn(C, generator=g))
+    zr = ops.bn_act(y, st, 0.2, res=res)
+    a = ops.up2_resize_act(ops.Lazy(y, st, res), B, H, W, th, tw, 0.2)
     assert a is not None and torch.equal(ops.up2_resize(zr, B, H, W, th, tw), a)
