@@ -717,6 +717,61 @@ int nsm_taa_resolve(const float* cur, const float* hist, const float* mv, const 
                     int B, int C, int H, int W, float scale_x, float scale_y, float blend,
                     int clamp, float depth_tol, float normal_cos, float* out,
                     unsigned char* accepted, void* stream);
+/* Spatiotemporal variance-guided filtering (SVGF, Schied et al. 2017), the
+ * denoiser of the paper's ray-tracing baseline (§4, Figure 9); its a-trous pass
+ * alone is a depth-aware post filter. Planar NCHW fp32; colour [B,C,H,W] with
+ * C = 1 or 3, depth [B,1,H,W], normals [B,3,H,W]. Luminance l = c for C = 1,
+ * 0.2126 r + 0.7152 g + 0.0722 b for C = 3. No atomics, no allocation, no
+ * synchronisation; every result is bitwise reproducible.
+ *   grad z(p): central differences of z with replicated edges,
+ *     gx = (z[x+] - z[x-]) / (x+ - x-), x+- = clamp(x +- 1, 0, W-1), 0 for W = 1;
+ *   edge weights of a tap q relative to p (q - p in pixels):
+ *     e_z = |z_p - z_q| / (sigma_z |grad z(p) . (q - p)| + 1e-8),
+ *     w_n = max(0, n_p . n_q)^sigma_n   (sigma_n = 0: 1).
+ * nsm_svgf_blocks: blocks per image of the two spatial passes; 0 for a shape no
+ *   pass supports (C other than 1 or 3, or what nsm_temporal_blocks refuses).
+ * nsm_svgf_accumulate: temporal accumulation on the lookup and the rejection
+ *   tests of nsm_taa_resolve (the same device functions; depth_prev and
+ *   normal_prev are the previous INPUT frame's; mv == NULL: no motion, nothing
+ *   rejected, depth and normals not read). hist_color [B,C,H,W], hist_moments
+ *   [B,2,H,W], hist_len [B,1,H,W] (fp32 holding integers): the previous
+ *   frame's outputs (hist_color possibly after filtering), all NULL for a first
+ *   frame. Accepted pixel: hN = hist_len at the nearest tap (floor(px + 0.5),
+ *   floor(py + 0.5)) clamped into the image, N = min(hN + 1, max_history),
+ *   a = max(alpha, 1/N), a_m = max(moments_alpha, 1/N), and with the bilinear
+ *   samples h of the history: c' = fmaf(1 - a, h_c - c, c),
+ *   m1' = fmaf(1 - a_m, h_m1 - l, l), m2' likewise with l^2. Rejected pixel or
+ *   first frame: N = 1, c' = c, m1' = l, m2' = l^2. out_var = max(0, m2' - m1'^2);
+ *   accepted (may be NULL) [B,1,H,W]: 1 where the history was used. No output
+ *   may be its own history.
+ * nsm_svgf_variance: pixels with hist_len < min_history get colour, m1 and m2
+ *   replaced by their means over the in-image taps of the 7x7 window weighted
+ *   by w = exp(-e_z) w_n (centre: 1), out_var = max(0, M2 - M1^2) *
+ *   (min_history / N); every other pixel passes colour and var through. The
+ *   moments themselves are only read.
+ * nsm_svgf_atrous: one iteration at `step` (2^i in iteration i), taps q = p +
+ *   step (dx, dy), dx, dy in [-2, 2], an out-of-image tap has weight 0 and is
+ *   not read; h = (1/16, 1/4, 3/8, 1/4, 1/16); centre weight h(0)^2, every other
+ *   tap w = h(dx) h(dy) exp(-e_z - |l_p - l_q| / phi_l) w_n with phi_l = sigma_l
+ *   sqrt(max(g, 0) + 1e-10), g the 3x3 Gaussian (1/4, 1/8, 1/16) of var with
+ *   replicated edges; out_color = sum w c_q / sum w, out_var = sum w^2 var_q /
+ *   (sum w)^2. var == NULL or sigma_l == 0: no luminance term, out_var not
+ *   written (may be NULL). out_color must not be color, out_var not var. */
+int nsm_svgf_blocks(int B, int C, int H, int W);
+int nsm_svgf_accumulate(const float* cur, const float* depth_cur, const float* normal_cur,
+                        const float* depth_prev, const float* normal_prev, const float* mv,
+                        const float* hist_color, const float* hist_moments, const float* hist_len,
+                        int B, int C, int H, int W, float scale_x, float scale_y, float alpha,
+                        float moments_alpha, int max_history, float depth_tol, float normal_cos,
+                        float* out_color, float* out_moments, float* out_len, float* out_var,
+                        unsigned char* accepted, void* stream);
+int nsm_svgf_variance(const float* color, const float* moments, const float* hist_len,
+                      const float* var, const float* depth, const float* normals, int B, int C,
+                      int H, int W, int min_history, float sigma_z, float sigma_n, float* out_color,
+                      float* out_var, void* stream);
+int nsm_svgf_atrous(const float* color, const float* var, const float* depth, const float* normals,
+                    int B, int C, int H, int W, int step, float sigma_z, float sigma_n,
+                    float sigma_l, float* out_color, float* out_var, void* stream);
 /* ---- feature sensitivity (the paper's §3.2, Eq. 1) --------------------------
  *   S_i = E[|phi(f_i + eps_i) - phi(f_i)|] / s_i,  eps_i ~ N(0, s_i) per pixel of
  *   channel i only,  s_i = factor * sigma[i] (formed once in fp32).

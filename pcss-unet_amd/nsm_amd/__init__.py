@@ -12,6 +12,7 @@ from .losses import (CustomLoss, EnhancedCustomLoss, L1Loss, PerturbationLoss,  
 from .temporal import (TemporalInstability, reproject,  # noqa: F401
                        temporal_instability_terms)
 from .taa import TemporalAA, taa_resolve, temporal_aa  # noqa: F401
+from .svgf import SVGF, atrous_filter, svgf, svgf_accumulate, svgf_variance  # noqa: F401
 from .optim import (FlatAdam, FlatAdamW, FlatSGD, allreduce_grads, flat_grad,  # noqa: F401
                     make_optimizer)
 from .grad_scaler import GradScaler  # noqa: F401

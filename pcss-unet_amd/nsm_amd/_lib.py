@@ -141,6 +141,11 @@ _SIGS = {
     "nsm_temporal_finalize": (I, [P, P, I, I, I, L, P, P, P, P, P]),
     "nsm_reproject": (I, [P, P, I, I, I, I, F, F, P, P, P]),
     "nsm_taa_resolve": (I, [P, P, P, P, P, P, P, I, I, I, I, F, F, F, I, F, F, P, P, P]),
+    "nsm_svgf_blocks": (I, [I, I, I, I]),
+    "nsm_svgf_accumulate": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, F, F, F, F, I, F, F, P, P, P,
+                                P, P, P]),
+    "nsm_svgf_variance": (I, [P, P, P, P, P, P, I, I, I, I, I, F, F, P, P, P]),
+    "nsm_svgf_atrous": (I, [P, P, P, P, I, I, I, I, I, F, F, F, P, P, P]),
     "nsm_sens_blocks": (I, [L]),
     "nsm_sens_variants": (I, [P, P, P, P, U64, I, I, I, I, I, I, F, I, I, P, P]),
     "nsm_sens_reduce": (I, [P, P, I, I, I, I, I, L, P, P]),
