@@ -364,6 +364,31 @@ int nsm_conv1x1_dgrad_bnbwd_h2(const void* dy2h, int M, int cop, const void* w2d
 int nsm_set_h2d_bnb_persist(int form, int grid, int* prev);
 int nsm_conv1x1_dgrad_bnbwd_h2_plan(int M, int cip, int cop, int* plan);
 int nsm_h2d_tile_walk(int gx, int gy, int grid, int block, int* out, int cap, int* count);
+/* nsm_bn_act_h2 and nsm_conv1x1_h2 in one kernel (csrc/nsm_conv_h2d.inc, "the
+ * fused BN-act 1x1 forward"): a1 [M][2 cin_p] h2 = lrelu(y1 * scale + shift)
+ * (* mask[row / HW], mask may be NULL) at the scale of `bound`, written for the
+ * weight gradient, and y2 [M][ldy2] fp32 = a1 wh^T + bias with the BN
+ * partials `stats` (may be NULL) of nsm_conv1x1_h2_rows(M, cout_p, 2 cin_p, 0)
+ * rows, the block producing its own A tile instead of reading a1 back. Same
+ * tile, product and K order, epilogue: a1, y2 and stats are bitwise those of
+ * the two entries. Covers shapes whose cout_p is exactly one block tile of
+ * the 1x1 GEMM (32, 64, 128 by M); any other shape is NSM_E_ARG.
+ * nsm_set_h2d_act_fuse: form 0 = policy (default; env NSM_H2D_ACT_FUSE=0), 1 =
+ * two kernels everywhere (env 1), 2 = fused wherever covered (env 2), < 0 =
+ * unchanged; grid = blocks of the fused kernel, which walk the M tiles
+ * blockIdx.x, + grid, ... (0 = one block per tile, < 0 = unchanged); prev (may
+ * be NULL) receives the previous {form, grid}. Host-wide, not per stream.
+ * nsm_bn_act_conv1x1_h2_plan: what the form in force runs for the shape:
+ * plan[0] = tile (as nsm_conv1x1_dgrad_bnbwd_h2_plan), plan[1] = 0 two kernels
+ * / 1 fused, plan[2] = the fused grid (0 for form 0), plan[3] = rows per
+ * partial row. */
+int nsm_bn_act_conv1x1_h2(const float* y1, int ldy1, int M, int cin_p, const float* scale,
+                          const float* shift, float slope, const float* mask, int HW, void* a1,
+                          const void* wh, const float* bias, int cout_p, float* y2, int ldy2,
+                          float* stats, const uint32_t* bound, const uint32_t* amax_w,
+                          void* stream);
+int nsm_set_h2d_act_fuse(int form, int grid, int* prev);
+int nsm_bn_act_conv1x1_h2_plan(int M, int cin_p, int cout_p, int* plan);
 size_t nsm_conv1x1_wgrad_h2_ws(int M, int cin_p, int cout_p);
 /* (amax_k1dz, modes 0 / 1, may be NULL: the slot receiving max|scale * dz|,
  * nsm_bn_bwd_finalize's bound term for an h2 dY1 from nsm_bn_bwd_apply_h2) */

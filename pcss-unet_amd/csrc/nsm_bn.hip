@@ -267,14 +267,19 @@ __global__ void __launch_bounds__(256) bn_act_h2_kernel(const float* __restrict_
                                                         const float* __restrict__ mask,
                                                         bf16_t* __restrict__ out, H2Scale hs) {
   const float s = exp2i(h2_exp(hs));  // every lane: amax_read is a wave reduction
-  const int ppb = blockDim.x / C8, tp = threadIdx.x / C8;
+  const int ppb = 256 / C8, tp = threadIdx.x / C8;  // (pix_launch_h2: whole waves)
+  if (tp >= ppb) return;
   const int c = (threadIdx.x - tp * C8) * 8;
   const F8 sc = ldf8(scale + c), sh = ldf8(shift + c);
   const int pstep = gridDim.x * ppb;
   for (int p = blockIdx.x * ppb + tp; p < M; p += pstep) {
-    F8 o = lrelu8(ld8(y + (size_t)p * ldy + c) * sc + sh, slope);
-    if (mask) o = o * ld8(mask + (size_t)fdiv((uint32_t)p, fdHW) * (C8 * 8) + c);
-    h2_store8(out + (size_t)p * 16 * C8, c, o, s);
+    F8 mk = f8zero();
+    if (mask) mk = ld8(mask + (size_t)fdiv((uint32_t)p, fdHW) * (C8 * 8) + c);
+    u32x4 h, l;
+    bn_act_h2_8(ld8(y + (size_t)p * ldy + c), sc, sh, slope, mask != nullptr, mk, s, h, l);
+    bf16_t* row = out + (size_t)p * 16 * C8;
+    *(u32x4*)(row + 2 * c) = h;
+    *(u32x4*)(row + 2 * c + 8) = l;
   }
 }
 
@@ -406,7 +411,8 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_h2_kernel(
     float slope, const float* __restrict__ mask, const float* __restrict__ mean,
     const float* __restrict__ coef, bf16_t* __restrict__ dy, H2Scale hs) {
   const float s = exp2i(h2_exp(hs));  // every lane: amax_read is a wave reduction
-  const int ppb = blockDim.x / C8, tp = threadIdx.x / C8;
+  const int ppb = 256 / C8, tp = threadIdx.x / C8;  // (pix_launch_h2: whole waves)
+  if (tp >= ppb) return;
   const int c = (threadIdx.x - tp * C8) * 8;
   const F8 sc = ldf8(scale + c), sh = ldf8(shift + c), mu = ldf8(mean + c);
   const F8 k1 = ldf8(coef + c), k2 = ldf8(coef + C + c), k3 = ldf8(coef + 2 * C + c);
@@ -429,6 +435,16 @@ static void pix_launch(long long M, int C8, dim3& grid, dim3& block) {
   g = g < 1 ? 1 : (g > 2048 ? 2048 : g);
   grid = dim3((unsigned)g);
   block = dim3((unsigned)tpb);
+}
+
+// pix_launch for the kernels that read an h2 scale (h2_exp reduces the 64
+// lines of the maximum slot across the wave: every lane of every wave must be
+// there): the block rounded up to whole waves, the lanes past the last pixel
+// group leave after the reduction. (C = 96: 252 threads left 4 lanes of the
+// last wave out and its rows took a maximum short of 4 lines.)
+static void pix_launch_h2(long long M, int C8, dim3& grid, dim3& block) {
+  pix_launch(M, C8, grid, block);
+  block.x = (block.x + 63u) & ~63u;
 }
 
 }  // namespace nsm
@@ -544,7 +560,7 @@ extern "C" int nsm_bn_act_h2(const float* y, int ldy, int M, int C, const float*
   NSM_CHECK_ARG(M >= 0 && M < (1 << 30), "bn_act_h2: too large");
   if (M == 0) return 0;
   dim3 g, b;
-  pix_launch(M, C / 8, g, b);
+  pix_launch_h2(M, C / 8, g, b);
   hipLaunchKernelGGL(bn_act_h2_kernel, g, b, 0, as_stream(stream), y, ldy, M, C / 8,
                      make_fastdiv(mask ? HW : 1), scale, shift, slope, mask, (bf16_t*)out,
                      H2Scale{bound, 1.f});
@@ -619,7 +635,7 @@ extern "C" int nsm_bn_bwd_apply_h2(const float* g, int ldg, const float* y, int 
   NSM_CHECK_ARG(M >= 0 && M < (1 << 30), "bn_bwd_apply_h2: too large");
   if (M == 0) return 0;
   dim3 gr, b;
-  pix_launch(M, C / 8, gr, b);
+  pix_launch_h2(M, C / 8, gr, b);
   hipLaunchKernelGGL(bn_bwd_apply_h2_kernel, gr, b, 0, as_stream(stream), g, ldg, y, ldy, M, C,
                      C / 8, make_fastdiv(mask ? HW : 1), scale, shift, slope, mask, mean, coef,
                      (bf16_t*)dy, H2Scale{bound, 1.f});

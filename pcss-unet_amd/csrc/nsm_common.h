@@ -305,12 +305,18 @@ __device__ __forceinline__ void h2_store4(bf16_t* row, int c, f32x4 v, float s) 
 }
 // 8 consecutive channels c..c+7 (c % 8 == 0) of one lane: h and l as one
 // 16-B word each (row = the h2 row of the pixel)
-__device__ __forceinline__ void h2_store8(bf16_t* row, int c, F8 v, float s) {
+__device__ __forceinline__ void h2_split8(F8 v, float s, u32x4& h, u32x4& l) {
   u32x2 ha, la, hb, lb;
   split4h(v.a, s, ha, la);
   split4h(v.b, s, hb, lb);
-  *(u32x4*)(row + 2 * c) = u32x4{ha.x, ha.y, hb.x, hb.y};
-  *(u32x4*)(row + 2 * c + 8) = u32x4{la.x, la.y, lb.x, lb.y};
+  h = u32x4{ha.x, ha.y, hb.x, hb.y};
+  l = u32x4{la.x, la.y, lb.x, lb.y};
+}
+__device__ __forceinline__ void h2_store8(bf16_t* row, int c, F8 v, float s) {
+  u32x4 h, l;
+  h2_split8(v, s, h, l);
+  *(u32x4*)(row + 2 * c) = h;
+  *(u32x4*)(row + 2 * c + 8) = l;
 }
 
 // ---- counter-based normal generator (nsm_tail.hip, nsm_sensitivity.hip) ------

@@ -5,6 +5,7 @@
 // the bf16 path's Winograd calls (wino_gemm_f16, wino_wgrad_gemm_f16). The
 // transforms that write the operands are Winograd kernels (nsm_conv.hip).
 #include "nsm_conv.h"
+#include "nsm_elem.h"  // bn_act_h2_8: the fused BN-act 1x1 forward (nsm_conv_h2d.inc)
 
 // the bf16 LDS-DMA loaders, which the direct 3x3 convolution on h2 operands
 // reuses (nsm_conv_h2d.inc: an h2 tensor read as 16-bit columns)

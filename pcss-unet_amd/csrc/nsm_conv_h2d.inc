@@ -659,6 +659,321 @@ extern "C" int nsm_h2d_tile_walk(int gx, int gy, int grid, int block, int* out, 
   return 0;
 }
 
+// ---- the fused BN-act 1x1 forward ------------------------------------------------
+// nsm_bn_act_h2 writes A1 = lrelu(BN1(Y1)) * mask as an h2 tensor and
+// nsm_conv1x1_h2 reads it straight back by LDS-DMA. Where N fits one block
+// tile, one block owns whole rows of A1, so gemm_h2a_kernel PRODUCES the A
+// stage instead of fetching it: every thread loads 8-channel units of Y1
+// (fp32, two 16-B loads), applies bn_act_h2_8 (nsm_elem.h, the arithmetic
+// bn_act_h2_kernel calls), stores the h2 words to A1 in global memory (the
+// weight gradient reads A1 later) and into the LDS A stage at the place
+// H2RowsDma would have put them: one 128-B row per M row and 64-column
+// K-tile, 16-B chunk c at (c ^ dswz<64>(row)); rows past M are zero, as the
+// DMA's out-of-range reads are. W2 streams into the B stage by LDS-DMA as in
+// gemm_h2_kernel. Fragments, mfma_h2's product order, the K order, the
+// epilogue (EpiStoreH) and BM are gemm_h2_kernel's, so Y2, the BN2 partials
+// and A1 are bitwise what the two kernels give.
+//
+// Schedule, per tile (a block walks tiles bm = blockIdx.x, + gridDim.x, ...):
+//   issue(t):  scale/shift (and mask) vectors, the Y1 units of K-tile t into
+//              registers, then W2's DMA pieces into stage t & 1
+//   commit(t): vmcnt(0); bn-act + split; ds_write the A stage; A1 stores
+//   prologue:  issue(0) commit(0) issue(1) barrier
+//   K-tile t:  k-step 0, k-step 1 | commit(t+1) barrier | issue(t+2)
+// Every vector-memory wait is a full one and each is meant: at commit(t+1)
+// the wave's counter holds, oldest first, the A1 stores of commit(t) and
+// issue(t+1)'s loads and DMA; the loads are the youngest and the counter is
+// in order, so waiting for them is waiting for all. Nothing else is in
+// flight in the K loop (a tile spanning images adds a drained mask load per
+// unit, see mrow). The next tile's first loads are younger than the
+// epilogue's Y2 stores and wait for them the same way.
+//
+// Budget per block (LDS: NSTG stages of (BM + BN) x 128 B, reused by
+// EpiStoreH; registers: accumulators + one k-step of fragments + NU units
+// of 8 fp32 + scale/shift + a mask row, capped at 256 by two waves per SIMD):
+//   256 x 128, 8 waves: 96 KB, NU = 2, 188 VGPRs -> one block per CU
+//   256 x 64,  4 waves: 80 KB, NU = 4, 207 VGPRs -> two
+//              (K = 64: one stage, 40 KB, 155 VGPRs -> three)
+//   128 x 128, 4 waves: 64 KB, NU = 2, 192 VGPRs -> two
+//   128 x 64,  4 waves: 48 KB, 180 VGPRs -> two (one stage: 24 KB, 143 -> three)
+//   128 x 32,  4 waves: 40 KB, NU = 2, 125 VGPRs -> four
+// No scratch in any of them (-Rpass-analysis=kernel-resource-usage); each
+// spills 8-49 SGPRs, which go to VGPR lanes and are inside the counts above.
+struct BnActH2P {
+  const float* y;  // Y1 [M][ldy]
+  int ldy;
+  const float* scale;
+  const float* shift;
+  float slope;
+  const float* mask;  // [B][cin_p] or NULL
+  FastDiv fdHW;
+  bf16_t* a1;  // [M][2 cin_p]
+};
+
+template <int BM, int BN, int WM, int WN, int NSTG>
+__global__ void __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(2)))
+    gemm_h2a_kernel(BnActH2P ap, H2RowsP bp, EpiStoreP ep, int M, int N, int K, int gx, H2Scale sca,
+                    H2Scale scb) {
+  constexpr int NW = WM * WN, NT = NW * 64, TM = BM / (WM * 32), TN = BN / (WN * 32);
+  using BL = H2RowsDma<BN, NW>;
+  constexpr int KT = 64;
+  constexpr int A_EL = BM * KT, STAGE = (BM + BN) * KT;
+  constexpr int NU = BM * 4 / NT, RSTEP = NT / 4;  // 8-channel units per thread and K-tile
+  static_assert(NU >= 1 && NU * NT == BM * 4, "unit shape");
+  constexpr int EPI = EpiStoreH::template lds_bytes<TM, TN, WM, WN>() / 2;
+  constexpr int LDS_EL = NSTG * STAGE > EPI ? NSTG * STAGE : EPI;
+  __shared__ __attribute__((aligned(1024))) bf16_t lds[LDS_EL];
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wid / WN, wn = wid % WN;
+  const int nk = K / KT;  // NSTG == 1: nk == 1
+  const int cin = K >> 1;
+  const int ea = h2_exp(sca), eb = h2_exp(scb);
+  const float s = exp2i(ea);
+  // unit i of a thread: row (tid >> 2) + i * RSTEP, channels 8 (tid & 3) .. + 7 of the K-tile
+  const bool masked = ap.mask != nullptr;
+
+  BL b;
+  b.init(bp, 0, 0, K, wid, lane, 0);
+  using FR = FragH2<false, KT>;
+  const int arb = wm * TM * 32, brb = wn * TN * 32;
+
+  for (int bm = blockIdx.x; bm < gx; bm += (int)gridDim.x) {
+    const int m0 = bm * BM;
+    if (bm != (int)blockIdx.x) __syncthreads();  // the previous tile's epilogue is done with the LDS
+    // Dropout2d mask rows: a tile inside one image (every tile of the step's
+    // shapes: BM divides H W) takes that image's vector per K-tile with the
+    // Y1 loads; a tile spanning images (HW % BM != 0) loads one vector per
+    // unit when it commits
+    const uint32_t b0 = masked ? fdiv((uint32_t)m0, ap.fdHW) : 0u;
+    const bool mrow = masked && fdiv((uint32_t)min(m0 + BM - 1, M - 1), ap.fdHW) != b0;
+
+    F8 yv[NU], sc, sh;
+    F8 mk0 = f8zero();
+    // (unit offsets from an opaque copy of the thread index, formed where they
+    // are used: hoisted, they would stay live across the K loop and the tiles)
+    auto issue = [&](int t) {
+      int tq = tid;
+      asm volatile("" : "+v"(tq));
+      const int c8 = tq & 3, r0 = tq >> 2;
+      const int c = t * 32 + c8 * 8;
+      sc = ldf8(ap.scale + c);
+      sh = ldf8(ap.shift + c);
+      if (masked && !mrow) mk0 = ld8(ap.mask + (size_t)b0 * cin + c);
+#pragma unroll
+      for (int i = 0; i < NU; ++i) {
+        const int m = min(m0 + r0 + i * RSTEP, M - 1);  // rows past M: a valid row, not used
+        yv[i] = ld8(ap.y + (size_t)m * ap.ldy + c);
+      }
+      b.prep(bp, t * KT);
+      const bf16_t* Bs = lds + (NSTG > 1 ? (t & 1) * STAGE : 0) + A_EL;
+#pragma unroll
+      for (int j = 0; j < BL::NI; ++j) b.one(bp, Bs, wid, j);
+    };
+    auto commit = [&](int t) {
+      vm_wait<0>();
+      int tq = tid;
+      asm volatile("" : "+v"(tq));
+      const int c8 = tq & 3, r0 = tq >> 2;
+      bf16_t* As = lds + (NSTG > 1 ? (t & 1) * STAGE : 0);
+#pragma unroll
+      for (int i = 0; i < NU; ++i) {
+        const int row = r0 + i * RSTEP, m = m0 + row;
+        const bool ok = m < M;
+        F8 mk = mk0;
+        if (mrow) {
+          F8 g = ld8(ap.mask + (size_t)fdiv((uint32_t)min(m, M - 1), ap.fdHW) * cin + t * 32 + c8 * 8);
+          // (consumed here: merged with the read of mk0, the load would become
+          // a flat load from a selected address and mk0 live in scratch)
+          asm volatile("" : "+v"(g.a), "+v"(g.b));
+          mk = g;
+        }
+        u32x4 h, l;
+        bn_act_h2_8(yv[i], sc, sh, ap.slope, masked, mk, s, h, l);
+        const u32x4 z = {0u, 0u, 0u, 0u};
+        h = ok ? h : z;
+        l = ok ? l : z;
+        const int sw = dswz<KT>(row);
+        *(u32x4*)&As[row * KT + (((2 * c8) ^ sw) << 3)] = h;
+        *(u32x4*)&As[row * KT + (((2 * c8 + 1) ^ sw) << 3)] = l;
+        if (ok) {
+          bf16_t* g = ap.a1 + (size_t)m * K + t * KT + c8 * 16;
+          *(u32x4*)g = h;
+          *(u32x4*)(g + 8) = l;
+        }
+      }
+    };
+
+    f32x16 acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+
+    issue(0);
+    commit(0);
+    if (NSTG > 1 && nk > 1) issue(1);
+    dma_barrier();
+
+    // one k-step of fragments at a time: the kernel is bound by the Y1 / A1 /
+    // Y2 streams, and the registers go to the Y1 units in flight instead
+    FR fa[2][TM], fb[2][TN];  // [plane][tm]
+    for (int t = 0; t < nk; ++t) {
+      const bf16_t* As = lds + (NSTG > 1 ? (t & 1) * STAGE : 0);
+      const bf16_t* Bs = As + A_EL;
+      int lq = lane;
+      asm volatile("" : "+v"(lq));
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+#pragma unroll
+          for (int tm = 0; tm < TM; ++tm) fa[p][tm].issue(As, arb + tm * 32, lq, ks, p);
+#pragma unroll
+          for (int tn = 0; tn < TN; ++tn) fb[p][tn].issue(Bs, brb + tn * 32, lq, ks, p);
+        }
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+          for (int tn = 0; tn < TN; ++tn) mfma_h2<TM, TN>(acc, fa, fb, tm, tn);
+        __builtin_amdgcn_s_setprio(0);
+      }
+      if constexpr (NSTG > 1) {
+        if (t + 1 < nk) {
+          // stage (t+1) & 1 was last read in K-tile t-1, before the barrier
+          // that ended it; this barrier: everyone's reads of stage t & 1
+          // retired (it is refilled next), everyone's part of K-tile t+1 landed
+          commit(t + 1);
+          dma_barrier();
+          if (t + 2 < nk) issue(t + 2);
+        }
+      }
+    }
+    dma_barrier();  // the epilogue reuses the LDS
+    const float ia = exp2i(-ea), ib = exp2i(-eb);
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j) acc[i][j] = (acc[i][j] * ia) * ib;
+    int le = lane;  // (opaque: the epilogue's lane offsets are formed here, not kept across the tiles)
+    asm volatile("" : "+v"(le));
+    EpiCtx cx{m0, 0, m0 + arb, brb, wm, wn, le, (float*)lds, bm, 0};
+    EpiStoreH::template apply<TM, TN, WM, WN>(ep, acc, cx, M, N, 0);
+  }
+}
+
+// NSM_H2D_ACT_FUSE: 0 (default) = the policy below, 1 = nsm_bn_act_h2 +
+// nsm_conv1x1_h2 everywhere, 2 = the fused kernel wherever it covers the
+// shape. nsm_set_h2d_act_fuse overrides (form 0 = policy, 1 = two kernels, 2 =
+// fused; grid = blocks of the fused kernel, 0 = one per tile).
+static int g_h2d_act_form = [] {
+  const long long v = env_int("NSM_H2D_ACT_FUSE", 0);
+  return v == 1 ? 1 : v == 2 ? 2 : 0;
+}();
+static int g_h2d_act_grid = 0;
+
+// shapes the fused kernel takes: N is exactly one block tile of h2d_tile (one
+// block then owns whole rows of A1 and produces each element once), whole
+// 64-column K-tiles (cin_p % 32 == 0)
+static int h2d_tile_bn(int t) { return t == 1 ? 256 : t == 2 || t == 3 ? 128 : t == 6 ? 32 : 64; }
+static bool h2d_act_covered(int tile, long long M, int N, int K) {
+  return tile >= 2 && tile <= 6 && h2d_tile_bn(tile) == N && K % 64 == 0 && K >= 64 &&
+         M * K < (1ll << 30);
+}
+// policy: every covered shape (the measurement kept all five of the fp32
+// step's, DESIGN.md "The fused BN-act 1x1 forward"; below them a launch less
+// is the whole difference)
+static bool h2d_act_fused(int tile, long long M, int N, int K) {
+  if (g_h2d_act_form == 1 || !h2d_act_covered(tile, M, N, K)) return false;
+  return true;
+}
+static int h2a_grid(int gx) { return g_h2d_act_grid > 0 ? std::min(g_h2d_act_grid, gx) : gx; }
+
+template <int BM, int BN, int WM, int WN>
+static int launch_h2a(const BnActH2P& ap, const H2RowsP& bp, const EpiStoreP& ep, int M, int N, int K,
+                      H2Scale sa, H2Scale sb, hipStream_t s) {
+  const int gx = ceil_div(M, BM), grid = h2a_grid(gx);
+  // a single K-tile needs one stage only (a second block per CU fits instead)
+  if (K == 64 && BN == 64)
+    hipLaunchKernelGGL((gemm_h2a_kernel<BM, BN, WM, WN, (BN == 64 ? 1 : 2)>), dim3(grid),
+                       dim3(WM * WN * 64), 0, s, ap, bp, ep, M, N, K, gx, sa, sb);
+  else
+    hipLaunchKernelGGL((gemm_h2a_kernel<BM, BN, WM, WN, 2>), dim3(grid), dim3(WM * WN * 64), 0, s, ap,
+                       bp, ep, M, N, K, gx, sa, sb);
+  NSM_LAUNCH_CHECK("bn_act_conv1x1_h2");
+  return 0;
+}
+
+// A1 [M][2 cin_p] h2 = lrelu(y1 * scale + shift) (* mask[row / HW]) at the
+// scale of `bound` (nsm_bn_act_h2) and y2 [M][ldy2] fp32 = A1 W^T + bias with
+// the BN partials `stats` (nsm_conv1x1_h2), in one kernel; the shape must be
+// one nsm_bn_act_conv1x1_h2_plan covers
+extern "C" int nsm_bn_act_conv1x1_h2(const float* y1, int ldy1, int M, int cin_p, const float* scale,
+                                     const float* shift, float slope, const float* mask, int HW,
+                                     void* a1, const void* wh, const float* bias, int cout_p,
+                                     float* y2, int ldy2, float* stats, const uint32_t* bound,
+                                     const uint32_t* amax_w, void* stream) {
+  NSM_CHECK_ARG(y1 && scale && shift && a1 && wh && y2 && bound && amax_w,
+                "bn_act_conv1x1_h2: null pointer");
+  NSM_CHECK_ARG(M > 0 && cin_p > 0 && cout_p > 0 && cin_p % 32 == 0 && cout_p % 32 == 0 &&
+                    ldy1 >= cin_p && ldy1 % 4 == 0 && ldy2 >= cout_p && ldy2 % 4 == 0 &&
+                    (!mask || HW > 0),
+                "bn_act_conv1x1_h2: bad shape");
+  NSM_CHECK_ARG(((uintptr_t)y1 % 16) == 0 && ((uintptr_t)a1 % 16) == 0 && ((uintptr_t)wh % 16) == 0 &&
+                    ((uintptr_t)y2 % 16) == 0 && ((uintptr_t)scale % 16) == 0 &&
+                    ((uintptr_t)shift % 16) == 0 && ((uintptr_t)mask % 16) == 0,
+                "bn_act_conv1x1_h2: 16-B alignment");
+  NSM_CHECK_ARG((long long)M * 2 * cin_p < (1ll << 30), "bn_act_conv1x1_h2: operand too large");
+  const int K = 2 * cin_p, tile = h2d_tile(M, cout_p, K, false);
+  if (!h2d_act_covered(tile, M, cout_p, K))
+    return fail(NSM_E_ARG, "bn_act_conv1x1_h2: shape not covered (cout_p %d, tile %d)", cout_p, tile);
+  BnActH2P ap{y1, ldy1, scale, shift, slope, mask, make_fastdiv(mask ? HW : 1), (bf16_t*)a1};
+  H2RowsP bp{(const bf16_t*)wh, K, cout_p, 0};
+  EpiStoreP ep{y2, ldy2, bias, stats, 0, nullptr, nullptr, 0.f, nullptr, 0, 1};
+  const H2Scale sa{bound, 1.f}, sb{amax_w, 1.f};
+  hipStream_t s = as_stream(stream);
+  switch (tile) {
+    case 2: return launch_h2a<256, 128, 4, 2>(ap, bp, ep, M, cout_p, K, sa, sb, s);
+    case 3: return launch_h2a<128, 128, 2, 2>(ap, bp, ep, M, cout_p, K, sa, sb, s);
+    case 4: return launch_h2a<256, 64, 4, 1>(ap, bp, ep, M, cout_p, K, sa, sb, s);
+    case 5: return launch_h2a<128, 64, 2, 2>(ap, bp, ep, M, cout_p, K, sa, sb, s);
+    default: return launch_h2a<128, 32, 4, 1>(ap, bp, ep, M, cout_p, K, sa, sb, s);
+  }
+}
+
+// form 0 = policy, 1 = two kernels, 2 = fused wherever covered, < 0 =
+// unchanged; grid = blocks of the fused kernel (0 = one per tile, < 0 =
+// unchanged). prev (optional) receives the previous {form, grid}.
+extern "C" int nsm_set_h2d_act_fuse(int form, int grid, int* prev) {
+  NSM_CHECK_ARG(form <= 2, "set_h2d_act_fuse: form %d", form);
+  if (prev) {
+    prev[0] = g_h2d_act_form;
+    prev[1] = g_h2d_act_grid;
+  }
+  if (form >= 0) g_h2d_act_form = form;
+  if (grid >= 0) g_h2d_act_grid = grid;
+  return 0;
+}
+
+// what ops.bn_act_conv1x1_h2 runs for (M, cin_p, cout_p): plan[0] = tile
+// (h2d_tile's numbering), plan[1] = form (0 = two kernels, 1 = fused), plan[2]
+// = blocks of the fused kernel (0 for form 0), plan[3] = rows per partial row
+extern "C" int nsm_bn_act_conv1x1_h2_plan(int M, int cin_p, int cout_p, int* plan) {
+  NSM_CHECK_ARG(plan && M > 0 && cin_p > 0 && cout_p > 0 && cin_p % 32 == 0 && cout_p % 32 == 0,
+                "bn_act_conv1x1_h2_plan: bad args");
+  const int K = 2 * cin_p, tile = h2d_tile(M, cout_p, K, false), bm = h2d_tile_bm(tile);
+  const bool f = h2d_act_fused(tile, M, cout_p, K);
+  plan[0] = tile;
+  plan[1] = f ? 1 : 0;
+  plan[2] = f ? h2a_grid(ceil_div(M, bm)) : 0;
+  plan[3] = bm;
+  return 0;
+}
+
 extern "C" size_t nsm_conv1x1_wgrad_h2_ws(int M, int cin_p, int cout_p) {
   return plan_wgrad_h2(M, cin_p, cout_p).ws_floats;
 }

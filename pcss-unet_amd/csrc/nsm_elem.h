@@ -29,6 +29,17 @@ __device__ __forceinline__ F8 lrelu8(F8 v, float slope) {
   return F8{lrelu4(v.a, slope), lrelu4(v.b, slope)};
 }
 
+// A1 = lrelu(y*scale+shift) (* mask[b][c], Dropout2d) of 8 channels as the h2
+// words h, l at scale s: the arithmetic of nsm_bn_act_h2, which the fused 1x1
+// forward (gemm_h2a_kernel, nsm_conv_h2d.inc) shares so that its A1 stays
+// bitwise the same
+__device__ __forceinline__ void bn_act_h2_8(F8 y, F8 sc, F8 sh, float slope, bool masked, F8 mk,
+                                            float s, u32x4& h, u32x4& l) {
+  F8 o = lrelu8(y * sc + sh, slope);
+  if (masked) o = o * mk;
+  h2_split8(o, s, h, l);
+}
+
 // dz = g * mask[b][c] * lrelu'(y*scale+shift)
 __device__ __forceinline__ f32x4 lrelu_grad4(f32x4 z, float slope) {
   return f32x4{lrelu_grad(z.x, slope), lrelu_grad(z.y, slope), lrelu_grad(z.z, slope),

@@ -81,6 +81,9 @@ _SIGS = {
     "nsm_set_h2d_bnb_persist": (I, [I, I, P]),
     "nsm_conv1x1_dgrad_bnbwd_h2_plan": (I, [I, I, I, P]),
     "nsm_h2d_tile_walk": (I, [I, I, I, I, P, I, P]),
+    "nsm_bn_act_conv1x1_h2": (I, [P, I, I, I, P, P, F, P, I, P, P, P, I, P, I, P, P, P, P]),
+    "nsm_set_h2d_act_fuse": (I, [I, I, P]),
+    "nsm_bn_act_conv1x1_h2_plan": (I, [I, I, I, P]),
     "nsm_conv3x3_h2_rows": (I, [I, I]),
     "nsm_conv3x3_h2": (I, [P, I, I, I, I, P, P, I, P, I, P, P, P, P]),
     "nsm_conv3x3_wgrad_h2_ws": (Z, [I, I, I, I, I]),

@@ -857,6 +857,60 @@ def conv1x1_h2(xh, wh, bias, cout_p, stats=True, amax=(None, None), tag=None):
     return y, part
 
 
+H2D_ACT_FORMS = ("policy", "two kernels", "fused")
+
+
+def set_h2d_act_fuse(form=-1, grid=-1):
+    """Kernel form of bn_act_conv1x1_h2 (nsm_set_h2d_act_fuse): form 0 /
+    "policy", 1 / "two kernels" (bn_act_h2 + conv1x1_h2), 2 / "fused" (wherever
+    the kernel covers the shape), -1 = unchanged; grid = blocks of the fused
+    kernel, 0 = one per tile, -1 = unchanged. Returns the previous (form, grid)."""
+    import ctypes
+    if isinstance(form, str):
+        form = H2D_ACT_FORMS.index(form)
+    prev = (ctypes.c_int * 2)()
+    call("nsm_set_h2d_act_fuse", int(form), int(grid), prev)
+    return prev[0], prev[1]
+
+
+def bn_act_conv1x1_h2_plan(M, cin_p, cout_p):
+    """(tile, form "two kernels" / "fused", fused grid, rows per partial row)
+    bn_act_conv1x1_h2 runs for this shape (nsm_bn_act_conv1x1_h2_plan)."""
+    import ctypes
+    plan = (ctypes.c_int * 4)()
+    call("nsm_bn_act_conv1x1_h2_plan", M, cin_p, cout_p, plan)
+    return plan[0], ("two kernels", "fused")[plan[1]], plan[2], plan[3]
+
+
+def bn_act_conv1x1_h2(y1, st, wh, bias, cout_p, slope=0.2, mask=None, HW=0, bound=None,
+                      amax_w=None, tag=None):
+    """A1 = bn_act_h2(y1) and its 1x1 conv (conv1x1_h2, with BN partials) as one
+    kernel that produces its own A tile (nsm_bn_act_conv1x1_h2) where the plan
+    says "fused", else as the two launches. bound: the slot bn_train(bound=...)
+    filled (A1's scale source), amax_w: wh's. Returns (A1 h2 [M, 2 cin_p], y
+    fp32 [M, cout_p], Partials); bitwise the same in both forms."""
+    from ._lib import lib
+    M, C = y1.shape
+    assert y1.dtype == F32 and wh.dtype == H2 and bound is not None and amax_w is not None
+    assert mask is None or HW > 0
+    if bn_act_conv1x1_h2_plan(M, C, cout_p)[1] != "fused":
+        a1 = bn_act_h2(y1, st, slope, mask=mask, HW=HW, bound=bound)
+        y, part = conv1x1_h2(a1, wh, bias, cout_p, stats=True, amax=(bound, amax_w), tag=tag)
+        return a1, y, part
+    a1 = torch.empty(M, 2 * C, dtype=H2, device=y1.device)
+    y = empty(M, cout_p, device=y1.device)
+    rpc = int(lib.nsm_conv1x1_h2_rows(M, cout_p, 2 * C, 0))
+    nchunk = -(-M // rpc)
+    part = Partials(empty(nchunk * 2 * cout_p, device=y1.device), nchunk, rpc)
+    ev = _probe(tag)
+    call("nsm_bn_act_conv1x1_h2", ptr(y1), y1.stride(0), M, C, ptr(st.scale), ptr(st.shift), slope,
+         ptr(mask), HW, ptr(a1), ptr(wh), ptr(bias), cout_p, ptr(y), y.stride(0), ptr(part.buf),
+         ptr(bound), ptr(amax_w), stream())
+    if ev is not None:
+        ev.record()
+    return a1, y, part
+
+
 def conv1x1_wgrad_h2(dyh, xh, cin, cout, dw, amax=(None, None), tag=None):
     """dw [cout, cin, 1, 1] <- sum_p dy (x) x over h2 pixel rows
     (nsm_conv1x1_wgrad_h2); amax = (scale source of dyh, of xh)."""

@@ -675,8 +675,9 @@ def _block_fwd(blk, X, B, H, W, training, mask, name="", pw=None, src=None, fuse
     eps1, eps2 = bn1m.eps, bn2m.eps
     w2 = pw.w2(ops.PACK_FWD)
     b2 = pw.vec("b2")
-    # h2 1x1 operands (fp32 training, csrc/nsm_conv_h2d.inc): A1 written by
-    # bn_act_h2, scaled from the bound the BN finalize records in AM_A1
+    # h2 1x1 operands (fp32 training, csrc/nsm_conv_h2d.inc): A1 written by the
+    # fused 1x1 forward or by bn_act_h2, scaled from the bound the BN finalize
+    # records in AM_A1
     h2x = training and w2.dtype == ops.H2
     if training:
         bn1 = ops.bn_train(Y1, bn1m, ci, bn1m.momentum, eps1, part=part1, gamma=pw.vec("g1"),
@@ -687,10 +688,12 @@ def _block_fwd(blk, X, B, H, W, training, mask, name="", pw=None, src=None, fuse
         bn1 = _bn_eval(bn1m, cip, ci, eps1, xin.device, pw.vec("g1"), pw.vec("be1"))
     A1 = None
     if h2x:
-        A1 = ops.bn_act_h2(Y1, bn1, SLOPE, mask=mask, HW=H * W, bound=_slot(am, AM_A1))
-        Y2, part2 = ops.conv1x1_h2(A1, w2, b2, cop, stats=True,
-                                   amax=(_slot(am, AM_A1), pw.amax_w2(ops.PACK_FWD)),
-                                   tag=name + ".conv.4.fwd")
+        # one kernel where cop fits one block tile (the block makes its own A
+        # tile from Y1 and writes A1 for the weight gradient), else the two
+        A1, Y2, part2 = ops.bn_act_conv1x1_h2(Y1, bn1, w2, b2, cop, SLOPE, mask=mask, HW=H * W,
+                                              bound=_slot(am, AM_A1),
+                                              amax_w=pw.amax_w2(ops.PACK_FWD),
+                                              tag=name + ".conv.4.fwd")
     elif BF16_MATERIALIZE_ACT if dtype in ops.S16 else F32_MATERIALIZE_ACT:
         # the same fp32 arithmetic and bf16 rounding as the fused operand prologue
         A1 = ops.bn_act(Y1, bn1, SLOPE, mask=mask, HW=H * W, amax=_slot(am, AM_A1))
